@@ -131,7 +131,7 @@ class TestRenderer:
         if g is None:
             g = torch.cuda.CUDAGraph()
             torch.cuda.current_stream().synchronize()
-            with torch.cuda.graph(g):
+            with vren.graph_capture(g):
                 self._run(first)
             self._graphs[first] = g
             # capture does not execute: run the frame opening for real below

@@ -833,7 +833,7 @@ class NGPTrainer:
             if tm is not None:
                 tm.arm()
             try:
-                with torch.cuda.graph(g):
+                with vren.graph_capture(g):
                     body()
             finally:
                 if tm is not None:

@@ -18,7 +18,9 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 import os
 from ctypes import c_float, c_int, c_int64, c_void_p
 
@@ -146,6 +148,25 @@ def lib():
 
 def _stream():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+@contextlib.contextmanager
+def graph_capture(g):
+    """torch.cuda.graph(g) with the cyclic garbage collector kept out of the
+    capture.  torch no longer collects before a capture, and a collection that
+    fires inside one may free an unreachable trainer or renderer whose
+    CUDAGraph destructor synchronises the device on ROCm: not allowed while a
+    stream is capturing, and thrown from a destructor it aborts the process.
+    So: collect first (dead graphs go now), no automatic collection inside."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(g):
+            yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 def _check(name, x, dtype=None):

@@ -17,6 +17,13 @@ field fwd/bwd, compositing + loss, [RCCL all-reduce], Adam).
 
 Run: python bench.py [--gpus N --steps K --warmup W]; for N>1 under
 torch.distributed.run (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* from the env).
+Such a plain run sets up, warms up, times the K steps and prints the result
+line (value, ms_per_step and what describes the timed window).  --full adds
+everything else to the line: the per-kernel breakdown, the roofline and
+occupancy-update windows, test PSNR, the test-render and drop-in timings,
+the CPU baseline and the quality checks.  --dump-outputs DIR writes what the
+timed path computes from a fixed, seeded state (dump_outputs) as
+DIR/<name>.npy, the same in every run up to the rounding of atomic sums.
 """
 from __future__ import annotations
 
@@ -96,6 +103,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=800)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--pretrain", type=int, default=2000, help="untimed setup training steps (steady-state occupancy)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel breakdown, roofline and occupancy-update "
+                         "windows, test PSNR, test-render and drop-in timings, CPU baseline, quality checks (a plain "
+                         "run sets up, warms up, times --steps steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computes from a fixed, seeded state to "
+                         "DIR/<name>.npy (float32; dump_outputs)")
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--scale", type=float, default=0.5)
     ap.add_argument("--res", type=int, default=800)
@@ -431,6 +445,51 @@ def transplant_state(src, dst):
     dst.invalidate_pre_encode()
 
 
+def dump_outputs(make_trainer, scene, gt_images, directions, poses, out_dir, write=True, steps=4, n_sample=1 << 20):
+    """--dump-outputs: what the timed path -- trainer.train_step's graph
+    replays, the trainer configured as the timed one -- computes from inputs
+    that are the same in every run, as float32 out_dir/<name>.npy.
+
+    The timed window itself cannot serve: its steps start from ~2500 training
+    steps whose gradient sums are float atomics, and training amplifies their
+    order (an occupancy cell flipped by rounding changes every later batch's
+    samples): two runs of one build differed by 0.7 % in the last step's
+    colours and 42 % in its parameters (relative L2).  So the path runs on a
+    state with no history: a trainer built like the timed one, a seeded random
+    hash table (every level carries signal), the scene's own occupancy
+    bitfield, no occupancy update, and learning rate 0 -- Adam runs, but its
+    first updates are +-lr by the SIGN of the gradient, which would turn the
+    rounding of a near-zero sum into a 2e-2 difference for the next step.
+    `steps` steps: the first eager (it marches the next batch ahead), then a
+    two-step replay and a one-step replay, as in the timed window.  Written:
+    the last step's per-ray losses (train_step's return value), colour,
+    opacity and depth, and a fixed, seeded sample of n_sample entries of Adam's
+    first moment (the gradients of the steps: march, field forward, compositing
+    and loss, MLP and hash backward, Adam all feed it).  Run to run these
+    differ by the rounding of the atomic sums alone."""
+    import numpy as np
+    import hashgrid as HG
+    tr = make_trainer(lr=0.0, warmup_steps=0, update_interval=10 ** 6)
+    with torch.no_grad():
+        g = torch.Generator().manual_seed(11)
+        tr.params[HG.MLP_PARAMS:tr.n_params] = ((torch.rand(tr.n_params - HG.MLP_PARAMS, generator=g) * 2 - 1)
+                                                * 0.5).to(tr.params.device)
+        tr.params16.copy_(tr.params.half())
+    tr.density_bitfield.copy_(scene.bitfield.to(tr.density_bitfield.device))
+    tr.global_step = 1  # (not a multiple of the update interval: the bitfield stays)
+    for i in range(steps):
+        tr.train_step(gt_images, directions, poses, allow_pair=i < steps - 1)
+    tr.drain()
+    torch.cuda.synchronize()
+    idx = torch.randint(tr.n_params, (n_sample,), generator=torch.Generator().manual_seed(0))
+    arrays = {"loss": tr.out_loss, "rgb": tr.out_rgb, "opacity": tr.out_op, "depth": tr.out_depth,
+              "exp_avg_sample": tr.exp_avg[idx.to(tr.exp_avg.device)]}
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, t in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     args = parse()
     world, rank, local = setup_dist(args)  # local: this rank's device index
@@ -441,11 +500,16 @@ def main():
     directions = scene.directions.to(dev).contiguous()
     poses = scene.poses.to(dev).contiguous()
     erode = args.erode == "on" or (args.erode == "auto" and args.scale > 0.5)
-    trainer = NGPTrainer(scale=args.scale, batch_size=args.batch, device=dev, hash_backward=args.hash_backward,
-                         bin_level_lo=args.bin_level_lo, bin_samples_per_ray=args.bin_samples_per_ray, erode=erode,
-                         bin_merge_hi=args.bin_merge_hi, pair_steps=not args.no_pair_steps, emulate_dp=args.emulate_dp,
-                         **({} if args.dp_fine_buckets is None else {"dp_fine_buckets": args.dp_fine_buckets}),
-                         **({} if args.chunk_first is None else {"chunk_first": args.chunk_first}))
+    def make_trainer(**kw):
+        """a trainer configured as the timed one (kw: what differs)"""
+        return NGPTrainer(scale=args.scale, batch_size=args.batch, device=dev, hash_backward=args.hash_backward,
+                          bin_level_lo=args.bin_level_lo, bin_samples_per_ray=args.bin_samples_per_ray, erode=erode,
+                          bin_merge_hi=args.bin_merge_hi, pair_steps=not args.no_pair_steps,
+                          emulate_dp=args.emulate_dp,
+                          **({} if args.dp_fine_buckets is None else {"dp_fine_buckets": args.dp_fine_buckets}),
+                          **({} if args.chunk_first is None else {"chunk_first": args.chunk_first}), **kw)
+
+    trainer = make_trainer()
     trainer.mark_invisible_cells(scene.K, scene.poses, (scene.W, scene.H))
     WORK = KERNEL_WORK
     R = args.batch
@@ -487,33 +551,6 @@ def main():
     torch.cuda.synchronize()
     log(rank, f"[bench] pretrain {args.pretrain} steps in {time.time() - t0:.1f}s, "
               f"samples last batch {int(trainer.n_samples.item())}")
-    # ---- breakdown region: graph replays whose graphs carry HIP events
-    # around every kernel (ktimer: external event nodes, read back one ring
-    # slot behind); per-kernel durations of the step as it runs in the graphs
-    n_bd = max(1, args.breakdown_steps)
-    full = KT.KernelTimer(trainer.dctr, rows=max(4096, 2 * n_bd))
-    trainer.timer = full
-    run(64)  # capture this timer's graph variants
-    torch.cuda.synchronize()
-    full.reset()
-    trainer.reset_stats()
-    s_bd = adam_steps()
-    t_bd = time.perf_counter()
-    run(n_bd)
-    torch.cuda.synchronize()
-    t_bd = (time.perf_counter() - t_bd) / n_bd
-    ran_bd = adam_steps() - s_bd
-    trainer.timer = None
-    bd_summary, bd_steps, bd_timeline = full.summary(), full.steps(), full.timeline()
-    marched_bd, composited_bd, active_bd, evaluated_bd = trainer.stat_totals()
-    if trainer.chunk_first <= 0:
-        evaluated_bd = marched_bd
-    fused_p = trainer.fused_params()
-    pw = {"params": trainer.params.numel(), "fused_params": fused_p, "adam_params": trainer.params.numel() - fused_p}
-    nb = max(1, ran_bd)  # (== n_bd: run() runs exactly n steps)
-    units_bd = {"marched": marched_bd / nb, "evaluated": evaluated_bd / nb, "composited": composited_bd / nb,
-                "active": active_bd / nb, **pw}
-
     def op_row(name, summary, units):
         """summary: {probe: (avg ms per launch, launches counted)}; every
         member is launched once per step in the rows counted"""
@@ -530,8 +567,40 @@ def main():
                 "kernels": members, "kernel_ms": {m: round(summary[m][0], 4) for m in members if m in summary},
                 "launches_timed": min((summary[m][1] for m in members if m in summary), default=0)}
 
-    kernels = {k: {"avg_launch_ms": round(v[0], 4), "launches_per_step": round(v[1], 2),
-                   "ms_per_step": round(v[0] * v[1], 4)} for k, v in sorted(bd_summary.items(), key=lambda kv: -kv[1][0] * kv[1][1])}
+    fused_p = trainer.fused_params()
+    pw = {"params": trainer.params.numel(), "fused_params": fused_p, "adam_params": trainer.params.numel() - fused_p}
+    n_bd = max(1, args.breakdown_steps)
+    if args.full:
+        # ---- breakdown region: graph replays whose graphs carry HIP events
+        # around every kernel (ktimer: external event nodes, read back one ring
+        # slot behind); per-kernel durations of the step as it runs in the graphs
+        full = KT.KernelTimer(trainer.dctr, rows=max(4096, 2 * n_bd))
+        trainer.timer = full
+        run(64)  # capture this timer's graph variants
+        torch.cuda.synchronize()
+        full.reset()
+        trainer.reset_stats()
+        s_bd = adam_steps()
+        t_bd = time.perf_counter()
+        run(n_bd)
+        torch.cuda.synchronize()
+        t_bd = (time.perf_counter() - t_bd) / n_bd
+        ran_bd = adam_steps() - s_bd
+        trainer.timer = None
+        bd_summary, bd_steps, bd_timeline = full.summary(), full.steps(), full.timeline()
+        marched_bd, composited_bd, active_bd, evaluated_bd = trainer.stat_totals()
+        if trainer.chunk_first <= 0:
+            evaluated_bd = marched_bd
+        nb = max(1, ran_bd)  # (== n_bd: run() runs exactly n steps)
+        units_bd = {"marched": marched_bd / nb, "evaluated": evaluated_bd / nb, "composited": composited_bd / nb,
+                    "active": active_bd / nb, **pw}
+        kernels = {k: {"avg_launch_ms": round(v[0], 4), "launches_per_step": round(v[1], 2),
+                       "ms_per_step": round(v[0] * v[1], 4)} for k, v in sorted(bd_summary.items(), key=lambda kv: -kv[1][0] * kv[1][1])}
+    else:
+        # the same number of plain steps, so that the timed window covers the same steps of the
+        # training run (the work per step follows the training state) with and without --full
+        run(64)
+        run(n_bd)
     # ---- timed region: plain graph replays (no instrumentation: even two
     # stamp kernels per step cost ~3 %)
     run(args.warmup)
@@ -552,6 +621,68 @@ def main():
     if ran_timed != args.steps:
         raise RuntimeError(f"timed window ran {ran_timed} steps, expected {args.steps}")
     marched, composited, active, evaluated = trainer.stat_totals()
+    if args.dump_outputs:
+        dump_outputs(make_trainer, scene, gt_images, directions, poses, args.dump_outputs, write=rank == 0)
+    t_max = torch.tensor([t_el], device=dev)
+    if world > 1:
+        dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
+    t_el = float(t_max.item())
+    total_rays = R * args.steps * world
+    value = total_rays / t_el
+    ms_step = t_el / args.steps * 1e3
+    if trainer.chunk_first <= 0:
+        evaluated = marched
+    units = {"marched": marched / args.steps, "evaluated": evaluated / args.steps,
+             "composited": composited / args.steps, "active": active / args.steps, **pw}
+    rm_s, vr_s, ev_s = units["marched"] / R, units["composited"] / R, units["evaluated"] / R
+
+    def result_line(loss, psnr=None):
+        """The result line of every run: the headline figure of the timed window and what describes it
+        (guard_hits: over the whole run up to this call)."""
+        # capacity guards (ngp_guard_hits): a device count clamped to its buffer's capacity anywhere in
+        # this run -- samples dropped -- would make the line's work smaller than the step's
+        guard_hits = int(vren.lib().ngp_guard_hits())
+        if guard_hits:
+            print(f"[bench] WARNING: {guard_hits} capacity guard hits (a device count clamped: work truncated)",
+                  file=sys.stderr)
+        return {
+            "metric": BASELINE["metric"], "value": round(value, 1), "unit": "rays/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "fp16 field (MLP forward, backward and weight gradients on fp16 MFMA operands, fp32 accumulate) / fp32 march, composite, Adam",
+            "data": "synthetic (analytic sphere+box scene, 100 views 800x800, Lego intrinsics; random-init weights "
+                    f"trained {args.pretrain} setup steps)",
+            "config": {"workload": (f"{'lego' if args.scale <= 0.5 else 'garden'}-shaped training step: {R} rays/rank, "
+                                    f"scale {args.scale:g}, {trainer.cascades} x 128^3 grid, L=16 F=2 T=2^19 hash, "
+                                    f"64-wide MLPs, raw loss, Adam lr 1e-2"),
+                       "batch_rays_per_gpu": R, "global_batch_rays": R * world, "pretrain_steps": args.pretrain,
+                       "rm_samples_per_ray": round(rm_s, 2), "vr_samples_per_ray": round(vr_s, 2),
+                       "field_evaluated_per_ray": round(ev_s, 2),
+                       "graphs": trainer.use_graphs,
+                       "chunk_first": trainer.chunk_first,
+                       "row_forward": trainer.row_forward if trainer._rows_fwd(trainer.chunk_first) else 0,
+                       "march_fork": trainer.march_fork_point(),
+                       "parallelism": f"dp{world}" + (f" (data-parallel step of world {args.emulate_dp} emulated: collectives as local copies)" if args.emulate_dp else ""), "last_loss": round(loss, 5),
+                       "hash_backward": args.hash_backward, "bin_level_lo": trainer.bin_level_lo,
+                       "bin_merge_hi": trainer.bin_merge_hi,
+                       "steps_per_graph_replay": 2 if trainer.pair_steps and world == 1 and not args.emulate_dp else 1,
+                       "erode": trainer.erode,
+                       "test_psnr_synthetic": round(psnr, 2) if psnr is not None else None},
+            # the timed window's step time per unit of its own work (the work per step follows the
+            # training state, so these compare runs whose windows landed on different phases)
+            "ns_per_composited_sample": round(ms_step * 1e6 / max(units["composited"], 1e-9), 4),
+            "ns_per_marched_sample": round(ms_step * 1e6 / max(units["marched"], 1e-9), 4),
+            "guard_hits": guard_hits,
+            "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
+            "full": bool(args.full),
+        }
+
+    if not args.full:  # a plain run: the headline figure alone
+        if rank == 0:
+            print(json.dumps(result_line(float(trainer.out_loss.sum().item()))), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # ---- roofline region: the same number of steps again, replaying the SAME
     # graphs as the timed window with the device probes armed (ktimer.ProbeTimer:
     # each probed kernel's execution span, no extra graph node); the steps that
@@ -623,17 +754,6 @@ def main():
     for k, r in ops.items():
         r["traffic"] = pmc_traffic(PMC_KEYS.get(k, []))
     dominant = max((k for k in ops if k != "mlp_fwd"), key=lambda k: ops[k]["ms_per_step"])
-    t_max = torch.tensor([t_el], device=dev)
-    if world > 1:
-        dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
-    t_el = float(t_max.item())
-    total_rays = R * args.steps * world
-    value = total_rays / t_el
-    if trainer.chunk_first <= 0:
-        evaluated = marched
-    units = {"marched": marched / args.steps, "evaluated": evaluated / args.steps,
-             "composited": composited / args.steps, "active": active / args.steps, **pw}
-    rm_s, vr_s, ev_s = units["marched"] / R, units["composited"] / R, units["evaluated"] / R
     # units per step of each window: every window's own counters over exactly its own steps
     # (the roofline's units and its probes cover the same replays).  Within a window the counts
     # must nest -- gradient-carrying <= field-evaluated <= marched, composited <= marched,
@@ -695,37 +815,9 @@ def main():
     oracle_q = None
     if rank == 0 and world == 1 and not args.no_oracle_quality:
         oracle_q = oracle_quality()
-    # capacity guards (ngp_guard_hits): a device count clamped to its buffer's capacity anywhere in
-    # this run -- samples dropped -- would make the line's work smaller than the step's
-    guard_hits = int(vren.lib().ngp_guard_hits())
-    if guard_hits:
-        print(f"[bench] WARNING: {guard_hits} capacity guard hits (a device count clamped: work truncated)",
-              file=sys.stderr)
-    ms_step = t_el / args.steps * 1e3
     if rank == 0:
         out = {
-            "metric": BASELINE["metric"], "value": round(value, 1), "unit": "rays/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "fp16 field (MLP forward, backward and weight gradients on fp16 MFMA operands, fp32 accumulate) / fp32 march, composite, Adam",
-            "data": "synthetic (analytic sphere+box scene, 100 views 800x800, Lego intrinsics; random-init weights "
-                    f"trained {args.pretrain} setup steps)",
-            "config": {"workload": (f"{'lego' if args.scale <= 0.5 else 'garden'}-shaped training step: {R} rays/rank, "
-                                    f"scale {args.scale:g}, {trainer.cascades} x 128^3 grid, L=16 F=2 T=2^19 hash, "
-                                    f"64-wide MLPs, raw loss, Adam lr 1e-2"),
-                       "batch_rays_per_gpu": R, "global_batch_rays": R * world, "pretrain_steps": args.pretrain,
-                       "rm_samples_per_ray": round(rm_s, 2), "vr_samples_per_ray": round(vr_s, 2),
-                       "field_evaluated_per_ray": round(ev_s, 2),
-                       "graphs": trainer.use_graphs,
-                       "chunk_first": trainer.chunk_first,
-                       "row_forward": trainer.row_forward if trainer._rows_fwd(trainer.chunk_first) else 0,
-                       "march_fork": trainer.march_fork_point(),
-                       "parallelism": f"dp{world}" + (f" (data-parallel step of world {args.emulate_dp} emulated: collectives as local copies)" if args.emulate_dp else ""), "last_loss": round(loss, 5),
-                       "hash_backward": args.hash_backward, "bin_level_lo": trainer.bin_level_lo,
-                       "bin_merge_hi": trainer.bin_merge_hi,
-                       "steps_per_graph_replay": 2 if trainer.pair_steps and world == 1 and not args.emulate_dp else 1,
-                       "erode": trainer.erode,
-                       "test_psnr_synthetic": round(psnr, 2) if psnr is not None else None},
+            **result_line(loss, psnr),
             "roofline": roof,
             "ops": ops,
             "kernels": kernels,
@@ -738,13 +830,7 @@ def main():
                                            "with an occupancy update left out; two steps per graph replay: "
                                            "alternately inside a graph and across a replay boundary)"},
             "step_bound": step_bound,
-            # the timed window's step time per unit of its own work (the work per step follows the
-            # training state, so these compare runs whose windows landed on different phases)
-            "ns_per_composited_sample": round(ms_step * 1e6 / max(units["composited"], 1e-9), 4),
-            "ns_per_marched_sample": round(ms_step * 1e6 / max(units["marched"], 1e-9), 4),
-            "guard_hits": guard_hits,
             "occupancy_update_step": update_step,
-            "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 4),
             "breakdown_note": (f"ops / kernels: wall-clock stamps around every kernel inside the captured graphs "
                                f"over {bd_steps} replayed steps ({t_bd * 1e3:.3f} ms/step with all stamps); timeline_us: "
                                f"average [start, end] of each launch (kernel#slot) from the step's first stamp, all "

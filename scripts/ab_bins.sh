@@ -7,7 +7,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 run() {
     name=$1; shift
-    timeout -k 10 200 python -u bench.py --steps 400 --warmup 10 --no-cpu-baseline --quality-steps 0 --psnr-views 0 \
+    timeout -k 10 200 python -u bench.py --full --steps 400 --warmup 10 --no-cpu-baseline --quality-steps 0 --psnr-views 0 \
         --infer-frames 0 "$@" > "$OUT/$name.json" 2> "$OUT/$name.err"
     python3 - "$OUT/$name.json" "$name" <<'PY'
 import json, sys

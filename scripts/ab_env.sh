@@ -14,7 +14,7 @@ for rep in $(seq 1 $REPS); do
     lib=$(echo "$cfg" | cut -d'|' -f1); envs=$(echo "$cfg" | cut -d'|' -f2); flags=$(echo "$cfg" | cut -d'|' -f3)
     LIB=ar-nerf_amd/lib/libngp_amd.so
     [ -n "$lib" ] && LIB=ar-nerf_amd/$lib/libngp_amd.so
-    env NGP_AMD_LIB=$PWD/$LIB $envs timeout -k 10 200 python -u bench.py --steps 1000 --warmup 10 --no-cpu-baseline \
+    env NGP_AMD_LIB=$PWD/$LIB $envs timeout -k 10 200 python -u bench.py --full --steps 1000 --warmup 10 --no-cpu-baseline \
         --quality-steps 0 --no-oracle-quality --psnr-views 0 --infer-frames 0 --dropin-steps 0 --breakdown-steps 20 $flags \
         > "$OUT/v${i}_$rep.json" 2> "$OUT/v${i}_$rep.err"
     python3 -c "

@@ -9,7 +9,7 @@ for rep in $(seq 1 $REPS); do
   i=0
   for flags in "$@"; do
     i=$((i+1))
-    timeout -k 10 300 python -u bench.py --scale 16 --batch 16384 --steps 300 --warmup 10 --no-cpu-baseline --quality-steps 0 \
+    timeout -k 10 300 python -u bench.py --full --scale 16 --batch 16384 --steps 300 --warmup 10 --no-cpu-baseline --quality-steps 0 \
         --psnr-views 0 --infer-frames 0 --no-oracle-quality --breakdown-steps 20 $flags > "$OUT/v${i}_$rep.json" 2> "$OUT/v${i}_$rep.err"
     python3 -c "
 import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); k=d['kernels']

@@ -17,7 +17,7 @@ for rep in $(seq 1 $REPS); do
     if [ "$lib" = base ]; then LIB=ar-nerf_amd/lib_base/libngp_amd.so
     elif [ -n "$lib" ]; then LIB=ar-nerf_amd/$lib/libngp_amd.so
     else LIB=ar-nerf_amd/lib/libngp_amd.so; fi
-    NGP_AMD_LIB=$PWD/$LIB timeout -k 10 200 python -u bench.py --steps 1000 --warmup 10 --no-cpu-baseline \
+    NGP_AMD_LIB=$PWD/$LIB timeout -k 10 200 python -u bench.py --full --steps 1000 --warmup 10 --no-cpu-baseline \
         --quality-steps 0 --no-oracle-quality --psnr-views 0 --infer-frames 0 --breakdown-steps 20 $flags \
         > "$OUT/v${i}_$rep.json" 2> "$OUT/v${i}_$rep.err"
     python3 -c "

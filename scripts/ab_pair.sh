@@ -18,7 +18,7 @@ run pair_$rep
 done
 run emulate_dp_1 --emulate-dp
 run emulate_dp_2 --emulate-dp
-timeout -k 10 300 rocprofv3 --kernel-trace -d "$OUT/tr" -o run -f csv -- python3 bench.py --steps 100 --warmup 5 \
+timeout -k 10 300 rocprofv3 --kernel-trace -d "$OUT/tr" -o run -f csv -- python3 bench.py --full --steps 100 --warmup 5 \
     --psnr-views 0 --no-cpu-baseline --breakdown-steps 1 --quality-steps 0 --infer-frames 0 > "$OUT/b.json" 2> "$OUT/b.err"
 for b in 10 11; do python3 scripts/timeline.py "$OUT/tr/run_kernel_trace.csv" 20 $b; done > "$OUT/timeline.txt"
 rm -rf "$OUT/tr"

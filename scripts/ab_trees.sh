@@ -1,5 +1,6 @@
 # Alternating A/B of whole source trees (a git worktree of an earlier commit, built in place, next to this one):
-# configs "TREE|ENV|FLAGS" (TREE "." = this tree), one bench line per run.
+# configs "TREE|ENV|FLAGS" (TREE "." = this tree), one bench line per run.  The samples per step come from the
+# line's roofline block: put --full into FLAGS for a tree whose bench.py has that option (earlier ones always print it).
 # usage: gpurun -- bash scripts/ab_trees.sh TAG REPS ".||" "abtree_r4||" ...
 set -e
 cd "$GRAFT_REPO_ROOT"
@@ -16,7 +17,7 @@ for rep in $(seq 1 $REPS); do
         --quality-steps 0 --no-oracle-quality --psnr-views 0 --infer-frames 0 --breakdown-steps 20 $flags \
         > "$OUT/v${i}_$rep.json" 2> "$OUT/v${i}_$rep.err")
     python3 -c "
-import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); u=d['roofline'].get('units_check',{})
+import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); u=d.get('roofline',{}).get('units_check',{})
 print('v'+sys.argv[2], sys.argv[3], round(d['value']/1e6,3), 'M rays/s', round(d['ms_per_step']*1e3,1), 'us/step', 'composited/step', round(u.get('composited_per_step',{}).get('timed',0)), 'evaluated/step', round(u.get('evaluated_per_step',{}).get('timed',0)))" "$OUT/v${i}_$rep.json" "$i" "[$cfg]"
   done
 done

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Recompute the bench line's per-op roofline fractions from a rocprofv3
-kernel trace of the SAME bench command (VERDICT r04 "Next" #1).
+kernel trace of the SAME bench command (VERDICT r04 "Next" #1); the command
+needs bench.py's --full, which runs the roofline window.
 
 bench.py brackets its roofline window -- the graph replays whose device
 probes give the line's `ops` / `roofline` -- with two trace_marker_kernel
