@@ -7,6 +7,25 @@
 
 namespace ngp {
 
+// ------------------------------------------------------------- AABB
+// (shared by the intersection / ray-generation kernels of march.hip and the
+// probe-ray kernel of probe.hip)
+__device__ __forceinline__ void aabb_t1t2(const float o[3], const float inv[3], const float* c,
+                                          const float* h, float& t1, float& t2) {
+    // intersection.cu:5-22
+    float lo[3], hi[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float tmin = (c[i] - h[i] - o[i]) * inv[i];
+        const float tmax = (c[i] + h[i] - o[i]) * inv[i];
+        lo[i] = fminf(tmin, tmax);
+        hi[i] = fmaxf(tmin, tmax);
+    }
+    t1 = fmaxf(fmaxf(lo[0], lo[1]), lo[2]);
+    t2 = fminf(fminf(hi[0], hi[1]), hi[2]);
+    if (t1 > t2) { t1 = -1.0f; t2 = -1.0f; }
+}
+
 // --------------------------------------------------------- marching
 struct MarchParams {
     const uint8_t* bitfield;

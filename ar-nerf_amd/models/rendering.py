@@ -43,11 +43,27 @@ def render(model, rays_o, rays_d, **kwargs):
 render_rays = render
 
 
+def _sh_light(kwargs, device):
+    """The SH_bkg kwarg as a device (9,3) fp32 tensor, or None when the frame
+    does not blend it: IM_bkg overrides it and blend_bkg=False skips both
+    (rendering.py:240-250)."""
+    sh = kwargs.get('SH_bkg', None)
+    if sh is None or kwargs.get('IM_bkg', None) is not None or not kwargs.get('blend_bkg', True):
+        return None
+    return torch.as_tensor(sh, dtype=torch.float32, device=device).reshape(9, 3).contiguous()
+
+
 def _background(kwargs, rays_d, default):
-    if kwargs.get('SH_bkg', None) is not None:
-        raise NotImplementedError("SH_bkg belongs to the AR-insertion app (insert/), out of scope")
+    """rgb_bg of rendering.py:240-247 for the torch blend: IM_bkg, else the
+    clamped SH_bkg light along rays_d (fp32 torch expressions), else default."""
     im = kwargs.get('IM_bkg', None)
-    return im if im is not None else default
+    if im is not None:
+        return im
+    sh = _sh_light(kwargs, rays_d.device)
+    if sh is not None:
+        import probes
+        return probes.get_SH_val(sh, rays_d.float(), clamp_postive=True, kernel=False)
+    return default
 
 
 def _test_renderer(model, n_rays, esf, T_threshold, max_samples):
@@ -74,17 +90,20 @@ def _test_renderer(model, n_rays, esf, T_threshold, max_samples):
 @torch.no_grad()
 def __render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
     """models/rendering.py:162-253 (grows samples per alive ray, composites
-    until T < T_threshold; black background by default).  For an NGP on the
+    until T < T_threshold; black background by default, SH_bkg / IM_bkg
+    blended behind the rays when given).  For an NGP on the
     GPU the loop runs device-resident in HIP graphs (renderer.TestRenderer,
     bit-identical results); device_loop=False keeps the host-driven loop."""
     exp_step_factor = kwargs.get('exp_step_factor', 0.)
     if kwargs.get('device_loop', True) and hasattr(model, '_shadow') and rays_o.is_cuda and len(rays_o) > 0:
         rr = _test_renderer(model, len(rays_o), exp_step_factor, kwargs.get('T_threshold', 1e-4),
                             kwargs.get('max_samples', MAX_SAMPLES))
-        out = rr.render(rays_o, rays_d, hits_t[:, 0])
+        # SH_bkg: blended by the frame's closing launch (ngp_render_test_finish_sh)
+        bg_sh = _sh_light(kwargs, rays_o.device)
+        out = rr.render(rays_o, rays_d, hits_t[:, 0], bg_sh=bg_sh)
         results = {k: v.clone() for k, v in out.items()}
-        rgb_bg = _background(kwargs, rays_d, torch.zeros(3, device=rays_o.device))
-        if kwargs.get('blend_bkg', True):
+        if bg_sh is None and kwargs.get('blend_bkg', True):
+            rgb_bg = _background(kwargs, rays_d, torch.zeros(3, device=rays_o.device))
             results['rgb'] += rgb_bg * (1 - results['opacity'])[:, None]
         return results
     results = {}
@@ -134,8 +153,8 @@ def __render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
     results['depth'] = depth
     results['rgb'] = rgb
     results['total_samples'] = total_samples
-    rgb_bg = _background(kwargs, rays_d, torch.zeros(3, device=device))
     if kwargs.get('blend_bkg', True):
+        rgb_bg = _background(kwargs, rays_d, torch.zeros(3, device=device))
         results['rgb'] += rgb_bg * (1 - opacity)[:, None]
     return results
 

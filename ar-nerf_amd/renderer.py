@@ -139,28 +139,35 @@ class TestRenderer:
 
     # --------------------------------------------------------------- API
     @torch.no_grad()
-    def render_loaded(self):
-        """Render the rays already in self.rays_o / rays_d / hits_t."""
+    def render_loaded(self, bg_sh=None):
+        """Render the rays already in self.rays_o / rays_d / hits_t.  bg_sh: a
+        device (9,3) SH9 light blended in behind the rays (SH_bkg,
+        rendering.py:241-250) in place of the constant background colour."""
         self._launch(True)
         while int(self.state[RS_ACTIVE].item()):
             self._launch(False)
         self.last_iterations = int(self.state[RS_ITERS].item())
-        vren._ok(HG._lib().ngp_render_test_finish(_p(self.opacity), self.n_rays, self.bg, _p(self.rgb),
-                                                  vren._stream()), "render_test_finish")
+        # (the finish runs outside the captured graphs: either one, no re-capture)
+        if bg_sh is not None:
+            vren.render_test_finish_sh(self.opacity, self.rays_d, bg_sh, self.rgb)
+        else:
+            vren._ok(HG._lib().ngp_render_test_finish(_p(self.opacity), self.n_rays, self.bg, _p(self.rgb),
+                                                      vren._stream()), "render_test_finish")
         return {"opacity": self.opacity, "depth": self.depth, "rgb": self.rgb,
                 "total_samples": self.state[RS_TOTAL]}
 
     @torch.no_grad()
-    def render(self, rays_o, rays_d, hits_t):
+    def render(self, rays_o, rays_d, hits_t, bg_sh=None):
         """__render_rays_test(model, rays_o, rays_d, hits_t) for hits_t (n_rays,2)
         (the caller's hits_t[:, 0], near-clamped): returns views of the
-        renderer's buffers (copy them to keep them past the next frame)."""
+        renderer's buffers (copy them to keep them past the next frame).
+        bg_sh: see render_loaded."""
         if rays_o.shape[0] != self.n_rays:
             raise RuntimeError(f"TestRenderer was built for {self.n_rays} rays, got {rays_o.shape[0]}")
         self.rays_o.copy_(rays_o.reshape(-1, 3))
         self.rays_d.copy_(rays_d.reshape(-1, 3))
         self.hits_t.copy_(hits_t.reshape(-1, 2))
-        return self.render_loaded()
+        return self.render_loaded(bg_sh)
 
     def set_camera(self, directions, center, half_size):
         """Per-pixel camera directions (H*W, 3) (datasets/ray_utils.py:7-42)

@@ -98,6 +98,9 @@ def _declare(L):
                                   c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "ngp_render_test_composite": [vp, vp, vp, vp, vp, c_int64, c_int, vp, vp, vp, c_float, vp, vp, vp, vp],
         "ngp_render_test_finish": [vp, c_int64, vp, vp, vp],
+        "ngp_probe_rays": [vp, vp, c_int, c_int64, c_int64, vp, vp, c_float, vp, vp, vp, vp],
+        "ngp_render_test_finish_sh": [vp, vp, c_int64, vp, vp, vp],
+        "ngp_probe_sh9_project": [vp, vp, vp, c_int64, c_int64, vp, vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)
@@ -216,6 +219,80 @@ def raygen_aabb(directions, poses, img_idxs, pix_idxs, center, half_size, near_d
                               float(near_distance), c_void_p(rays_o.data_ptr()), c_void_p(rays_d.data_ptr()),
                               c_void_p(hits_t.data_ptr()), _stream()), "raygen_aabb")
     return rays_o, rays_d, hits_t
+
+
+# --------------------------------------------------------- light probes
+def probe_rays(pts, dirs, center, half_size, near_distance, out=None):
+    """ngp_probe_rays: R rays from each of the P points `pts` (P,3) along
+    `dirs`, one shared (R,3) set or (P,R,3) per probe; AABB + near clamp as
+    models/rendering.py:29-31.  Returns rays_o, rays_d (P*R,3) and hits_t
+    (P*R,2), written into `out` = (rays_o, rays_d, hits_t) when given."""
+    pp, pd = _check("pts", pts, torch.float32), _check("dirs", dirs, torch.float32)
+    if pts.dim() != 2 or pts.shape[1] != 3 or dirs.dim() not in (2, 3) or dirs.shape[-1] != 3:
+        raise RuntimeError("pts must be (P,3) and dirs (R,3) or (P,R,3)")
+    P, R, per_probe = pts.shape[0], dirs.shape[-2], int(dirs.dim() == 3)
+    if per_probe and dirs.shape[0] != P:
+        raise RuntimeError(f"dirs holds {dirs.shape[0]} probes, pts {P}")
+    n = P * R
+    if out is None:
+        out = tuple(torch.empty(n, k, device=pts.device) for k in (3, 3, 2))
+    rays_o, rays_d, hits_t = out
+    for name, t, k in (("rays_o", rays_o, 3), ("rays_d", rays_d, 3), ("hits_t", hits_t, 2)):
+        _check(name, t, torch.float32)
+        if t.numel() != n * k:
+            raise RuntimeError(f"{name} must hold {n} rays")
+    _ok(lib().ngp_probe_rays(pp, pd, per_probe, P, R, _check("center", center, torch.float32),
+                             _check("half_size", half_size, torch.float32), float(near_distance),
+                             c_void_p(rays_o.data_ptr()), c_void_p(rays_d.data_ptr()), c_void_p(hits_t.data_ptr()),
+                             _stream()), "probe_rays")
+    return rays_o, rays_d, hits_t
+
+
+def _check_shec(shec):
+    p = _check("shec", shec, torch.float32)
+    if tuple(shec.shape) != (9, 3):
+        raise RuntimeError(f"shec must be (9,3), got {tuple(shec.shape)}")
+    return p
+
+
+def render_test_finish_sh(opacity, rays_d, shec, rgb):
+    """ngp_render_test_finish_sh, in place on rgb (N,3):
+    rgb += relu(get_SH_val(shec, rays_d)) * (1 - opacity)."""
+    n = opacity.numel()
+    if rays_d.numel() != 3 * n or rgb.numel() != 3 * n:
+        raise RuntimeError("opacity (N), rays_d (N,3) and rgb (N,3) must agree")
+    _ok(lib().ngp_render_test_finish_sh(_check("opacity", opacity, torch.float32),
+                                        _check("rays_d", rays_d, torch.float32), n, _check_shec(shec),
+                                        _check("rgb", rgb, torch.float32), _stream()), "render_test_finish_sh")
+    return rgb
+
+
+def probe_sh9_project(rays_d, rgb, opacity=None, rgb_sh=None, trans_sh=None):
+    """ngp_probe_sh9_project: rays_d, rgb (P,R,3) [, opacity (P,R)] ->
+    rgb_sh (P,9,3) [, trans_sh (P,9) of 1 - opacity; None without opacity].
+    Outputs are written into rgb_sh / trans_sh when given."""
+    if rays_d.dim() != 3 or rays_d.shape[-1] != 3 or rgb.shape != rays_d.shape:
+        raise RuntimeError("rays_d and rgb must be (P,R,3)")
+    P, R = rays_d.shape[:2]
+    pd, pc = _check("rays_d", rays_d, torch.float32), _check("rgb", rgb, torch.float32)
+    po = None
+    if opacity is not None:
+        po = _check("opacity", opacity, torch.float32)
+        if opacity.numel() != P * R:
+            raise RuntimeError("opacity must be (P,R)")
+        if trans_sh is None:
+            trans_sh = torch.empty(P, 9, device=rays_d.device)
+    elif trans_sh is not None:
+        raise RuntimeError("trans_sh needs opacity")
+    if rgb_sh is None:
+        rgb_sh = torch.empty(P, 9, 3, device=rays_d.device)
+    _check("rgb_sh", rgb_sh, torch.float32)
+    if rgb_sh.numel() != P * 27 or (trans_sh is not None and trans_sh.numel() != P * 9):
+        raise RuntimeError("rgb_sh must be (P,9,3) and trans_sh (P,9)")
+    pt = _check("trans_sh", trans_sh, torch.float32) if trans_sh is not None else None
+    _ok(lib().ngp_probe_sh9_project(pd, pc, po, P, R, c_void_p(rgb_sh.data_ptr()), pt, _stream()),
+        "probe_sh9_project")
+    return rgb_sh, trans_sh
 
 
 # -------------------------------------------------------- occupancy grid

@@ -275,6 +275,41 @@ int ngp_render_test_composite(const float* sigmas, const float* rgbs, const floa
 /* rgb += bg_rgb (host float[3]) * (1 - opacity) (rendering.py:240-251) */
 int ngp_render_test_finish(const float* opacity, int64_t n_rays, const float* bg_rgb, float* rgb, void* stream);
 
+/* ------------------------------------------------------- light probes */
+/* The insertion app's light probes (insert/main.py:306-407): R rays from each
+ * of P scene points, the global light blended in behind them as an SH9
+ * background (SH_bkg, models/rendering.py:241-250), and the SH9 projection of
+ * the radiance and of 1 - opacity (insert/insert_utils.py:132-136).  SH9
+ * basis in the app's order (insert_utils.py:102-127), d = (x, y, z):
+ *   Y0 = 0.2820947918, Y1..3 = 0.4886025119 (y, z, x), Y4 = 1.0925484306 xy,
+ *   Y5 = 1.0925484306 yz, Y6 = 0.3153915653 (3z^2 - 1), Y7 = 1.0925484306 xz,
+ *   Y8 = 0.5462742153 (x^2 - y^2).
+ * No atomics in any of the three: results are run-to-run bit-identical.
+ *
+ * Probe rays: rays_o[p*R+r] = pts[p] (pts (P,3)); rays_d[p*R+r] = dirs[r]
+ * (dirs (R,3), dirs_per_probe = 0) or dirs[p*R+r] (dirs (P,R,3),
+ * dirs_per_probe = 1); hits_t (P*R,2) = the AABB interval of
+ * ngp_ray_aabb_intersect (one box, max_hits 1) with the near clamp of
+ * models/rendering.py:29-31, bit for bit.  P*R < 2^31; R = 0 with P > 0 is
+ * an error. */
+int ngp_probe_rays(const float* pts, const float* dirs, int dirs_per_probe, int64_t P, int64_t R,
+                   const float* center, const float* half_size, float near_distance, float* rays_o, float* rays_d,
+                   float* hits_t, void* stream);
+/* rgb += relu(sum_k Y_k(rays_d) shec[k]) * (1 - opacity): get_SH_val(SH_bkg,
+ * rays_d, clamp_postive=True) and the blend of rendering.py:241-250.  shec is
+ * a DEVICE (9,3) f32 tensor (a light that changes between calls needs no
+ * host read); rays_d (n_rays,3), opacity (n_rays), rgb (n_rays,3) in place. */
+int ngp_render_test_finish_sh(const float* opacity, const float* rays_d, int64_t n_rays, const float* shec, float* rgb,
+                              void* stream);
+/* rgb_sh[p,k,c] = (4 pi / R) sum_r Y_k(rays_d[p,r]) rgb[p,r,c]  (P,9,3) and,
+ * when trans_sh is non-null, trans_sh[p,k] = (4 pi / R) sum_r Y_k (1 -
+ * opacity[p,r])  (P,9): get_SH_coeff on both quantities of main.py:399-406.
+ * rays_d, rgb (P,R,3), opacity (P,R; may be null with trans_sh) are only
+ * read.  One workgroup per probe, fixed summation order.  Any R >= 1,
+ * P*R < 2^31; R = 0 with P > 0 is an error. */
+int ngp_probe_sh9_project(const float* rays_d, const float* rgb, const float* opacity, int64_t P, int64_t R,
+                          float* rgb_sh, float* trans_sh, void* stream);
+
 /* --------------------------------------------- hash grid + fused MLPs */
 /* Level table of tcnn's Grid/Hash encoding as configured at
  * models/networks.py:33-49 (host function; fp32 arithmetic like tcnn).
