@@ -280,7 +280,14 @@ def test_fused_adam_matches_separate_adam(spr):
     agree to the fp64-summed gradient's rounding (bit-identical almost
     everywhere), the rest to atomic-order noise, and the gradient buffer is
     left all zero for the next step.  spr=1: a workspace too small for the
-    batch (overflow) -- every bucket takes the residual path."""
+    batch (overflow) -- every bucket takes the residual path.
+
+    Both runs start from ZERO moments at step 1, so a bucket without records
+    computes 0 from 0 and both sides share adam_elem: this is a comparison of
+    two launches of the product.  The fused Adam from non-zero moments, at
+    step_dev 999, with grad_scale != 1, on flagged, multi-chunk and empty
+    buckets, against an independent fp64 Adam, is test_hashbin_gpu.py's
+    test_fused_adam_matches_fp64_adam."""
     import hashgrid as HG
     outs = []
     for fused in (True, False):
