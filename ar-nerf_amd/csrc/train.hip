@@ -159,7 +159,8 @@ __device__ __forceinline__ int64_t composite_loss_ray(
     if (la.lambda_depth != 0.f) {
         const float v = D / la.depth_scale + 1e-10f;
         loss += -la.lambda_depth * logf(fminf(v, 1.0f)) * la.inv_n_rays;
-        if (v < 1.0f) gdep = -la.lambda_depth / v / la.depth_scale * la.inv_n_rays;
+        // (torch's clip(max=1) passes the gradient at v == 1 too, as nerf_loss_bw_kernel does)
+        if (v <= 1.0f) gdep = -la.lambda_depth / v / la.depth_scale * la.inv_n_rays;
     }
     // ---- distortion loss (losses.py:77-80): its forward over the composited
     // samples (W_tot = O, WT_tot = D are the ray's sums of ws and ws*ts) and
@@ -1560,6 +1561,10 @@ int ngp_density_grid_ema(float* density_grid, uint64_t* grid_key, int64_t n, flo
 // reference's expression rounded in fp32 in its order (x.detach() in the rgb
 // denominator carries no gradient; division by the grid scale is torch's
 // multiplication by its reciprocal; clip's gradient is 0 where it clips).
+// One deliberate exception: the log loss's backward divides (g 0.7607) by a =
+// 0.2935 + x once, where autograd divides by (a / b) and then by b -- the same
+// value to within a few fp32 roundings (tests/composite_ref.py bounds both), not the
+// same bits.
 // loss_type 0 raw, 2 log, 3 tanh (the reference's set).
 __device__ __forceinline__ float nerf_rgb_term(int type, float x, float y, float& dtdx) {
     if (type == 0) {

@@ -29,7 +29,12 @@ _LOSS_TYPE = {'raw': 0, 'log': 2, 'tanh': 3}
 class _NeRFLossFn(torch.autograd.Function):
     """NeRFLoss's per-ray rgb / opacity / depth terms (losses.py:63-76) and their
     backward, one launch each way (ngp_nerf_loss_fw / _bw) instead of ~15
-    elementwise ops and their autograd nodes; the same expressions op for op."""
+    elementwise ops and their autograd nodes; the same expressions op for op,
+    except that the log loss's backward divides by (0.2935 + x) once where
+    autograd divides by the ratio and then by (0.2935 + gt): equal to within a
+    few fp32 roundings, not bit for bit.  All four tensors must describe the same n
+    rays (rgb and gt (n, 3); opacity and depth n elements): the kernels index
+    them by ray without looking at their shapes -- NeRFLoss.forward checks."""
 
     @staticmethod
     def forward(ctx, rgb, gt, opacity, depth, loss_type, lam_op, lam_depth, grid_scale):
@@ -82,11 +87,12 @@ class NeRFLoss(nn.Module):
         d = {}
         rgb, gt, op, dep = results['rgb'], target['rgb'], results['opacity'], results['depth']
         if all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-               for t in (rgb, gt, op, dep)) and rgb.dim() == 2 and rgb.shape[1] == 3:
+               for t in (rgb, gt, op, dep)) and rgb.dim() == 2 and rgb.shape[1] == 3 and gt.shape == rgb.shape \
+                and all(tuple(t.shape) in ((rgb.shape[0],), (rgb.shape[0], 1)) for t in (op, dep)):
             d['rgb'], d['opacity'], d['depth'] = _NeRFLossFn.apply(rgb, gt, op, dep, self.loss_type,
                                                                     float(self.lambda_opacity),
                                                                     float(self.lambda_depth), float(self.grid_scale))
-        else:  # (the reference's torch expressions, e.g. for CPU tensors)
+        else:  # (the reference's torch expressions: CPU tensors, a broadcast gt, opacity / depth of another shape)
             d['rgb'] = self.rgb_loss(rgb, gt) ** 2
             o = op + 1e-10
             d['opacity'] = self.lambda_opacity * (-o * torch.log(o))
