@@ -289,6 +289,28 @@ __device__ __forceinline__ float sigmoid_h(_Float16 o) {
     return (float)(_Float16)(1.0f / (1.0f + expf(-(float)o)));
 }
 
+// Colour output of the rgb_net row o (networks.py:68-78, 152-157) in mode act
+// (NGP_RGB_*, wave-uniform: a scalar branch): the sigmoid, the raw value
+// (rgb_act='None'), F.leaky_relu on the fp16 row as torch evaluates it (fp32
+// opmath, slope 0.01f, rounded to half; o == 0 takes the slope branch) for
+// raw-HDR training, and relu for output_radiance.
+__device__ __forceinline__ float rgb_out(_Float16 o, int act) {
+    if (act == NGP_RGB_SIGMOID) return sigmoid_h(o);
+    const float f = (float)o;
+    if (act == NGP_RGB_NONE || f > 0.f) return f;
+    return act == NGP_RGB_LEAKY_RELU ? (float)(_Float16)(f * 0.01f) : 0.f;
+}
+
+// dL/do of rgb_out from the upstream g (fp32)
+__device__ __forceinline__ float rgb_out_grad(_Float16 o, float g, int act) {
+    if (act == NGP_RGB_SIGMOID) {
+        const float y = 1.0f / (1.0f + expf(-(float)o));
+        return g * (y * (1.0f - y));
+    }
+    if (act == NGP_RGB_NONE || (float)o > 0.f) return g;
+    return act == NGP_RGB_LEAKY_RELU ? g * 0.01f : 0.f;
+}
+
 // ENC_IN: the encoding comes from ngp_hash_encode (pair-major enc_in with
 // row stride enc_stride) instead of being gathered here.
 template <bool COLOR, bool ENC_IN = false>
@@ -300,7 +322,8 @@ __global__ void __launch_bounds__(256) field_fwd_kernel(const float* __restrict_
                                                         _Float16* __restrict__ h_out,
                                                         const _Float16* __restrict__ enc_in = nullptr,
                                                         int64_t enc_stride = 0,
-                                                        const int32_t* __restrict__ sidx = nullptr) {
+                                                        const int32_t* __restrict__ sidx = nullptr,
+                                                        int act = NGP_RGB_SIGMOID) {
     __shared__ __attribute__((aligned(16))) _Float16 sw[SWF];
     __shared__ LevelLds lv;
     load_fwd_weights_direct(mlp, sw, COLOR);
@@ -340,9 +363,9 @@ __global__ void __launch_bounds__(256) field_fwd_kernel(const float* __restrict_
             h4 h3[4], h4v[4];
             const h4 o = color_net(cin, sw, s, g, h3, h4v);
             if (valid && g == 0) {
-                rgbs[3 * i] = sigmoid_h(o[0]);
-                rgbs[3 * i + 1] = sigmoid_h(o[1]);
-                rgbs[3 * i + 2] = sigmoid_h(o[2]);
+                rgbs[3 * i] = rgb_out(o[0], act);
+                rgbs[3 * i + 1] = rgb_out(o[1], act);
+                rgbs[3 * i + 2] = rgb_out(o[2], act);
             }
         }
     }
@@ -597,7 +620,7 @@ __global__ void __launch_bounds__(64 * FEM2_WAVES, FEM2_WAVES / 2) field_encode_
     const float* __restrict__ xyzs, const float* __restrict__ dirs, int64_t n, const int64_t* __restrict__ n_dev,
     const int32_t* __restrict__ sidx, GridArgs ga, const uint32_t* __restrict__ table,
     const _Float16* __restrict__ mlp, _Float16* __restrict__ enc_pm, float* __restrict__ sigmas,
-    float* __restrict__ rgbs, _Float16* __restrict__ h_out) {
+    float* __restrict__ rgbs, _Float16* __restrict__ h_out, int act) {
     __shared__ __attribute__((aligned(16))) _Float16 sw[SWF];
     __shared__ LevelLds lv;
     NGP_PROBE_BEGIN(NGP_P_FIELD_ENCODE_MLP);
@@ -678,9 +701,9 @@ __global__ void __launch_bounds__(64 * FEM2_WAVES, FEM2_WAVES / 2) field_encode_
                 h4 h3[4], h4v[4];
                 const h4 o = color_net(cin, sw, s, g, h3, h4v);
                 if (ok && g == 0) {
-                    rgbs[3 * (int64_t)ic] = sigmoid_h(o[0]);
-                    rgbs[3 * (int64_t)ic + 1] = sigmoid_h(o[1]);
-                    rgbs[3 * (int64_t)ic + 2] = sigmoid_h(o[2]);
+                    rgbs[3 * (int64_t)ic] = rgb_out(o[0], act);
+                    rgbs[3 * (int64_t)ic + 1] = rgb_out(o[1], act);
+                    rgbs[3 * (int64_t)ic + 2] = rgb_out(o[2], act);
                 }
             }
         }
@@ -698,7 +721,8 @@ __device__ __forceinline__ float encode_mlp_chunk(const float* __restrict__ xyzs
                                                   int64_t i0, int cnt, int64_t n, const GridArgs& ga,
                                                   const LevelLds& lv, const uint32_t* __restrict__ table,
                                                   const _Float16* sw, _Float16* __restrict__ enc_pm,
-                                                  float* __restrict__ sigmas, float* __restrict__ rgbs, int pre = 0) {
+                                                  float* __restrict__ sigmas, float* __restrict__ rgbs, int pre = 0,
+                                                  int act = NGP_RGB_SIGMOID) {
     int lane_l = threadIdx.x & 63;  // (opaque: lane-derived addresses are rematerialised, not held)
     asm volatile("" : "+v"(lane_l));
     const int s = lane_l & 15, g = lane_l >> 4;
@@ -756,9 +780,9 @@ __device__ __forceinline__ float encode_mlp_chunk(const float* __restrict__ xyzs
             h4 h3[4], h4v[4];
             const h4 o = color_net(cin, sw, s, g, h3, h4v);
             if (ok && g == 0) {
-                rgbs[3 * ic] = sigmoid_h(o[0]);
-                rgbs[3 * ic + 1] = sigmoid_h(o[1]);
-                rgbs[3 * ic + 2] = sigmoid_h(o[2]);
+                rgbs[3 * ic] = rgb_out(o[0], act);
+                rgbs[3 * ic + 1] = rgb_out(o[1], act);
+                rgbs[3 * ic + 2] = rgb_out(o[2], act);
             }
         }
     }
@@ -788,7 +812,7 @@ __global__ void __launch_bounds__(64 * FEM2_WAVES, FEM2_WAVES / 2) field_first_c
     int64_t n_rows, int64_t n, float T_thr, GridArgs ga, const uint32_t* __restrict__ table,
     const _Float16* __restrict__ mlp, _Float16* __restrict__ enc_pm, float* __restrict__ sigmas,
     float* __restrict__ rgbs, int32_t* __restrict__ rest, int32_t* __restrict__ list2, int64_t* __restrict__ total2,
-    int64_t* __restrict__ evaluated, int pre) {
+    int64_t* __restrict__ evaluated, int pre, int act) {
     __shared__ __attribute__((aligned(16))) _Float16 sw[SWF];
     __shared__ LevelLds lv;
     __shared__ unsigned long long blk_eval;
@@ -815,7 +839,7 @@ __global__ void __launch_bounds__(64 * FEM2_WAVES, FEM2_WAVES / 2) field_first_c
         if (cnt > 0) {
             const float dl = lane < cnt ? deltas[start + lane] : 0.f;
             const float sg = encode_mlp_chunk<COLOR>(xyzs, dirs, start, cnt, n, ga, lv, table, sw, enc_pm, sigmas, rgbs,
-                                                     pre);
+                                                     pre, act);
             const float om = 1.0f - (1.0f - __expf(-sg * dl));  // chunk_segments_kernel's expression
             const ChunkT ct = chunk_transmittance(om, cnt, 1.0f, T_thr, lane);
             rc = (!ct.hit && N > 64) ? (int32_t)(N - 64) : 0;
@@ -1251,7 +1275,8 @@ __device__ __forceinline__ void coop_dw(const _Float16* scr, int w, int s, int g
 __global__ void __launch_bounds__(64 * CW, CW / 4) field_bwd_mlp_coop_kernel(
     const float* __restrict__ dirs, int64_t n, const int64_t* __restrict__ n_dev, const int32_t* __restrict__ sidx,
     const _Float16* __restrict__ enc, const _Float16* __restrict__ mlp, const float* __restrict__ dL_dsig,
-    const float* __restrict__ dL_drgb, float* __restrict__ denc, float* __restrict__ grad_mlp, int64_t enc_pm_stride) {
+    const float* __restrict__ dL_drgb, float* __restrict__ denc, float* __restrict__ grad_mlp, int64_t enc_pm_stride,
+    int act) {
     extern __shared__ __attribute__((aligned(16))) _Float16 smem[];
     // per-wave minima of the layers' per-sample exponents (double-buffered by iteration parity)
     __shared__ __attribute__((aligned(16))) int emin[2][5][CW];
@@ -1344,13 +1369,12 @@ __global__ void __launch_bounds__(64 * CW, CW / 4) field_bwd_mlp_coop_kernel(
         h4 h3[4], h4v[4];
         const h4 o = color_net(pack(shh, hh), sw, s, g, h3, h4v);
         NGP_BWD_PHASE(1);
-        // ---- output layer: sigmoid backward on rows 0..2
+        // ---- output layer: the colour activation's backward on rows 0..2
         f4 dout = z;
         if (g == 0) {
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
-                const float y = 1.0f / (1.0f + expf(-(float)o[r]));
-                dout[r] = cur.gr[r] * (y * (1.0f - y));
+                dout[r] = rgb_out_grad(o[r], cur.gr[r], act);
             }
         }
         const int Eo = next_exp(sample_max(max4(dout)), 0);
@@ -1603,7 +1627,7 @@ __global__ void __launch_bounds__(256) rep_reduce_kernel(float* __restrict__ gra
 
 static int launch_bwd_mlp(const float* dirs, int64_t n, const int64_t* n_dev, const int32_t* sample_idx,
                           const void* enc_f16, int64_t enc_pm_stride, const void* mlp_f16, const float* dL_dsigmas,
-                          const float* dL_drgbs, float* denc_ws, float* grad_mlp, void* stream) {
+                          const float* dL_drgbs, float* denc_ws, float* grad_mlp, int act, void* stream) {
     static bool attr_set = false;
     const size_t clds = (size_t)COOP_LDS_HALFS * sizeof(_Float16);
     if (!attr_set) {
@@ -1617,7 +1641,7 @@ static int launch_bwd_mlp(const float* dirs, int64_t n, const int64_t* n_dev, co
     const unsigned cb = persistent_blocks(n, CW * 16, ccap);
     NGP_TIMED(NGP_K_MLP_BWD, s, field_bwd_mlp_coop_kernel<<<cb, 64 * CW, clds, s>>>(
         dirs, n, n_dev, sample_idx, (const _Float16*)enc_f16, (const _Float16*)mlp_f16, dL_dsigmas, dL_drgbs, denc_ws,
-        grad_mlp, enc_pm_stride));
+        grad_mlp, enc_pm_stride, act));
     return ngp_launch_status();
 }
 
@@ -1627,9 +1651,20 @@ using namespace ngp;
 
 extern "C" {
 
+// a colour mode outside NGP_RGB_* is refused before anything else is looked at
+#define NGP_CHECK_RGB_ACT(a) NGP_CHECK_ARG((a) >= NGP_RGB_SIGMOID && (a) <= NGP_RGB_RELU)
+
 int ngp_field_forward(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
                       const ngp_hashgrid_t* grid, const void* table_f16, const void* mlp_f16, float* sigmas,
                       float* rgbs, void* enc_f16, void* h_f16, void* stream) {
+    return ngp_field_forward_act(xyzs, dirs, n, n_dev, grid, table_f16, mlp_f16, sigmas, rgbs, enc_f16, h_f16,
+                                 NGP_RGB_SIGMOID, stream);
+}
+
+int ngp_field_forward_act(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                          const ngp_hashgrid_t* grid, const void* table_f16, const void* mlp_f16, float* sigmas,
+                          float* rgbs, void* enc_f16, void* h_f16, int rgb_act, void* stream) {
+    NGP_CHECK_RGB_ACT(rgb_act);
     GridArgs ga;
     int st = grid_args(grid, ga);
     if (st) return st;
@@ -1641,7 +1676,7 @@ int ngp_field_forward(const float* xyzs, const float* dirs, int64_t n, const int
     static const unsigned cap = resident_blocks(field_fwd_kernel<true>, 256, 0);
     field_fwd_kernel<true><<<persistent_blocks(n, 64, cap), 256, 0, as_stream(stream)>>>(
         xyzs, dirs, n, n_dev, ga, (const uint32_t*)table_f16, (const _Float16*)mlp_f16, sigmas, rgbs,
-        (_Float16*)enc_f16, (_Float16*)h_f16);
+        (_Float16*)enc_f16, (_Float16*)h_f16, nullptr, 0, nullptr, rgb_act);
     return ngp_launch_status();
 }
 
@@ -1699,6 +1734,15 @@ int ngp_hash_encode(const float* xyzs, int64_t n, const int64_t* n_dev, const in
 int ngp_field_encode_mlp(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
                          const int32_t* sample_idx, const ngp_hashgrid_t* grid, const void* table_f16,
                          const void* mlp_f16, void* enc_pm, float* sigmas, float* rgbs, void* h_f16, void* stream) {
+    return ngp_field_encode_mlp_act(xyzs, dirs, n, n_dev, sample_idx, grid, table_f16, mlp_f16, enc_pm, sigmas, rgbs,
+                                    h_f16, NGP_RGB_SIGMOID, stream);
+}
+
+int ngp_field_encode_mlp_act(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                             const int32_t* sample_idx, const ngp_hashgrid_t* grid, const void* table_f16,
+                             const void* mlp_f16, void* enc_pm, float* sigmas, float* rgbs, void* h_f16, int rgb_act,
+                             void* stream) {
+    NGP_CHECK_RGB_ACT(rgb_act);
     GridArgs ga;
     int st = grid_args(grid, ga);
     if (st) return st;
@@ -1712,13 +1756,13 @@ int ngp_field_encode_mlp(const float* xyzs, const float* dirs, int64_t n, const 
         static const unsigned capd = resident_blocks(field_encode_mlp_reg_kernel<false>, 64 * FEM2_WAVES, 0);
         NGP_TIMED(NGP_K_HASH_ENCODE, s, field_encode_mlp_reg_kernel<false><<<std::max(1u, std::min(capd, (unsigned)((n + 64 * FEM2_WAVES - 1) / (64 * FEM2_WAVES)))), 64 * FEM2_WAVES, 0, s>>>(
             xyzs, nullptr, n, n_dev, sample_idx, ga, (const uint32_t*)table_f16, (const _Float16*)mlp_f16,
-            (_Float16*)enc_pm, sigmas, nullptr, (_Float16*)h_f16));
+            (_Float16*)enc_pm, sigmas, nullptr, (_Float16*)h_f16, NGP_RGB_SIGMOID));
         return ngp_launch_status();
     }
     static const unsigned capr = resident_blocks(field_encode_mlp_reg_kernel<true>, 64 * FEM2_WAVES, 0);
     NGP_TIMED(NGP_K_HASH_ENCODE, s, field_encode_mlp_reg_kernel<true><<<std::max(1u, std::min(capr, (unsigned)((n + 64 * FEM2_WAVES - 1) / (64 * FEM2_WAVES)))), 64 * FEM2_WAVES, 0, s>>>(
         xyzs, dirs, n, n_dev, sample_idx, ga, (const uint32_t*)table_f16, (const _Float16*)mlp_f16,
-        (_Float16*)enc_pm, sigmas, rgbs, (_Float16*)h_f16));
+        (_Float16*)enc_pm, sigmas, rgbs, (_Float16*)h_f16, rgb_act));
     return ngp_launch_status();
 }
 
@@ -1727,6 +1771,18 @@ int ngp_field_forward_first_pre(const float* xyzs, const float* dirs, const floa
                                 float T_threshold, const ngp_hashgrid_t* grid, const void* table_f16,
                                 const void* mlp_f16, void* enc_pm, float* sigmas, float* rgbs, int32_t* rest,
                                 int32_t* list2, int64_t* total2, int64_t* evaluated, int pre_levels, void* stream) {
+    return ngp_field_forward_first_pre_act(xyzs, dirs, deltas, rays_a, rows, n_rows_dev, n_rows, n, T_threshold, grid,
+                                           table_f16, mlp_f16, enc_pm, sigmas, rgbs, rest, list2, total2, evaluated,
+                                           pre_levels, NGP_RGB_SIGMOID, stream);
+}
+
+int ngp_field_forward_first_pre_act(const float* xyzs, const float* dirs, const float* deltas, const int64_t* rays_a,
+                                    const int32_t* rows, const int64_t* n_rows_dev, int64_t n_rows, int64_t n,
+                                    float T_threshold, const ngp_hashgrid_t* grid, const void* table_f16,
+                                    const void* mlp_f16, void* enc_pm, float* sigmas, float* rgbs, int32_t* rest,
+                                    int32_t* list2, int64_t* total2, int64_t* evaluated, int pre_levels, int rgb_act,
+                                    void* stream) {
+    NGP_CHECK_RGB_ACT(rgb_act);
     NGP_CHECK_ARG(pre_levels == 0 || (pre_levels == PRE_LEVELS && enc_pm));
     GridArgs ga;
     int st = grid_args(grid, ga);
@@ -1743,7 +1799,8 @@ int ngp_field_forward_first_pre(const float* xyzs, const float* dirs, const floa
     const unsigned blocks = std::max(1u, std::min(cap, (unsigned)((n_rows + FEM2_WAVES - 1) / FEM2_WAVES)));
     NGP_TIMED(NGP_K_HASH_ENCODE, s, field_first_chunk_kernel<true><<<blocks, 64 * FEM2_WAVES, 0, s>>>(
         xyzs, dirs, deltas, rays_a, rows, n_rows_dev, n_rows, n, T_threshold, ga, (const uint32_t*)table_f16,
-        (const _Float16*)mlp_f16, (_Float16*)enc_pm, sigmas, rgbs, rest, list2, total2, evaluated, pre_levels));
+        (const _Float16*)mlp_f16, (_Float16*)enc_pm, sigmas, rgbs, rest, list2, total2, evaluated, pre_levels,
+        rgb_act));
     return ngp_launch_status();
 }
 
@@ -1802,12 +1859,21 @@ int ngp_field_mlp_forward(const void* enc_pm, const float* dirs, int64_t n, cons
 int ngp_field_backward_mlp(const float* dirs, int64_t n, const int64_t* n_dev, const int32_t* sample_idx,
                            const void* enc_f16, int64_t enc_pm_stride, const void* mlp_f16, const float* dL_dsigmas,
                            const float* dL_drgbs, float* denc_ws, float* grad_mlp, void* stream) {
+    return ngp_field_backward_mlp_act(dirs, n, n_dev, sample_idx, enc_f16, enc_pm_stride, mlp_f16, dL_dsigmas,
+                                      dL_drgbs, denc_ws, grad_mlp, NGP_RGB_SIGMOID, stream);
+}
+
+int ngp_field_backward_mlp_act(const float* dirs, int64_t n, const int64_t* n_dev, const int32_t* sample_idx,
+                               const void* enc_f16, int64_t enc_pm_stride, const void* mlp_f16,
+                               const float* dL_dsigmas, const float* dL_drgbs, float* denc_ws, float* grad_mlp,
+                               int rgb_act, void* stream) {
+    NGP_CHECK_RGB_ACT(rgb_act);
     NGP_CHECK_ARG(n >= 0);
     if (n == 0) return NGP_OK;
     NGP_CHECK_ARG(dirs && enc_f16 && mlp_f16 && dL_dsigmas && dL_drgbs && denc_ws && grad_mlp);
     NGP_CHECK_ARG(((uintptr_t)mlp_f16 & 15) == 0);
     return launch_bwd_mlp(dirs, n, n_dev, sample_idx, enc_f16, enc_pm_stride, mlp_f16, dL_dsigmas, dL_drgbs,
-                          denc_ws, grad_mlp, stream);
+                          denc_ws, grad_mlp, rgb_act, stream);
 }
 
 int ngp_hash_backward(const float* xyzs, int64_t n, const int64_t* n_dev, const int32_t* sample_idx,
@@ -1888,11 +1954,20 @@ int ngp_field_backward(const float* xyzs, const float* dirs, int64_t n, const in
                        const ngp_hashgrid_t* grid, const void* enc_f16, const void* mlp_f16,
                        const float* dL_dsigmas, const float* dL_drgbs, float* denc_ws, float* grad_mlp,
                        float* grad_table, void* stream) {
+    return ngp_field_backward_act(xyzs, dirs, n, n_dev, grid, enc_f16, mlp_f16, dL_dsigmas, dL_drgbs, denc_ws,
+                                  grad_mlp, grad_table, NGP_RGB_SIGMOID, stream);
+}
+
+int ngp_field_backward_act(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                           const ngp_hashgrid_t* grid, const void* enc_f16, const void* mlp_f16,
+                           const float* dL_dsigmas, const float* dL_drgbs, float* denc_ws, float* grad_mlp,
+                           float* grad_table, int rgb_act, void* stream) {
+    NGP_CHECK_RGB_ACT(rgb_act);
     GridArgs ga;
     int st = grid_args(grid, ga);
     if (st) return st;
-    st = ngp_field_backward_mlp(dirs, n, n_dev, nullptr, enc_f16, 0, mlp_f16, dL_dsigmas, dL_drgbs, denc_ws, grad_mlp,
-                                stream);
+    st = ngp_field_backward_mlp_act(dirs, n, n_dev, nullptr, enc_f16, 0, mlp_f16, dL_dsigmas, dL_drgbs, denc_ws,
+                                    grad_mlp, rgb_act, stream);
     if (st) return st;
     return ngp_hash_backward(xyzs, n, n_dev, nullptr, grid, denc_ws, grad_table, stream);
 }

@@ -22,6 +22,8 @@ import torch
 import vren
 
 N_LEVELS = 16
+# colour-output modes of the field kernels (include/ngp_amd.h NGP_RGB_*)
+RGB_SIGMOID, RGB_NONE, RGB_LEAKY_RELU, RGB_RELU = 0, 1, 2, 3
 MLP_PARAMS = 10240
 OW = {"W1": (0, 64, 32), "W2": (2048, 16, 64), "W3": (3072, 64, 32), "W4": (5120, 64, 64), "W5": (9216, 16, 64)}
 
@@ -53,6 +55,13 @@ def _lib():
                                               vp, vp, vp, vp, vp]
         L.ngp_field_forward_first_pre.argtypes = [vp, vp, vp, vp, vp, vp, c_int64, c_int64, c_float, P, vp, vp, vp,
                                                   vp, vp, vp, vp, vp, vp, c_int, vp]
+        # colour-output modes (raw-HDR models): the base signatures with rgb_act before the stream
+        L.ngp_field_forward_act.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, c_int, vp]
+        L.ngp_field_backward_act.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, vp, c_int, vp]
+        L.ngp_field_backward_mlp_act.argtypes = [vp, c_int64, vp, vp, vp, c_int64, vp, vp, vp, vp, vp, c_int, vp]
+        L.ngp_field_encode_mlp_act.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, vp, vp, vp, c_int, vp]
+        L.ngp_field_forward_first_pre_act.argtypes = [vp, vp, vp, vp, vp, vp, c_int64, c_int64, c_float, P, vp, vp,
+                                                      vp, vp, vp, vp, vp, vp, vp, c_int, c_int, vp]
         L.ngp_field_encode_first_coarse.argtypes = [vp, vp, vp, vp, c_int64, c_int64, P, vp, vp, vp]
         L.ngp_hash_backward.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp]
         L.ngp_hash_backward_binned.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp, c_int64, c_int, c_int, vp]
@@ -78,7 +87,8 @@ def _lib():
                   L.ngp_hash_backward_levels_rep,
                   L.ngp_hash_binned_plan, L.ngp_hash_binned_apply, L.ngp_hash_binned_write,
                   L.ngp_hash_binned_accum, L.ngp_hash_binned_accum_levels, L.ngp_hash_binned_apply_adam,
-                  L.ngp_hash_binned_accum_adam):
+                  L.ngp_hash_binned_accum_adam, L.ngp_field_forward_act, L.ngp_field_backward_act,
+                  L.ngp_field_backward_mlp_act, L.ngp_field_encode_mlp_act, L.ngp_field_forward_first_pre_act):
             f.restype = c_int
         _declared = True
     return L
@@ -139,8 +149,9 @@ def _check(x, name, dtype, numel=None):
         raise RuntimeError(f"{name} must have {numel} elements, got {x.numel()}")
 
 
-def field_forward(xyzs, dirs, grid: HashGrid, params16, save_enc=True, n_dev=None, want_h=False):
-    """Fused NGP.forward (models/networks.py:133-146) -> sigmas (n), rgbs (n,3), enc (n,32) fp16 | None, h | None"""
+def field_forward(xyzs, dirs, grid: HashGrid, params16, save_enc=True, n_dev=None, want_h=False, rgb_act=0):
+    """Fused NGP.forward (models/networks.py:133-146) -> sigmas (n), rgbs (n,3), enc (n,32) fp16 | None, h | None
+    rgb_act: the colour-output mode RGB_* (networks.py:152-157)."""
     n = xyzs.shape[0]
     dev = xyzs.device
     _check(xyzs, "xyzs", torch.float32); _check(dirs, "dirs", torch.float32)
@@ -149,10 +160,10 @@ def field_forward(xyzs, dirs, grid: HashGrid, params16, save_enc=True, n_dev=Non
     rgb = torch.empty(n, 3, device=dev)
     enc = torch.empty(n, 32, dtype=torch.float16, device=dev) if save_enc else None
     h = torch.empty(n, 16, dtype=torch.float16, device=dev) if want_h else None
-    st = _lib().ngp_field_forward(_ptr(xyzs), _ptr(dirs), n, _ptr(n_dev), ctypes.byref(grid.desc),
-                                  _ptr(params16[MLP_PARAMS:]), _ptr(params16), _ptr(sig), _ptr(rgb), _ptr(enc),
-                                  _ptr(h), vren._stream())
-    vren._ok(st, "ngp_field_forward")
+    st = _lib().ngp_field_forward_act(_ptr(xyzs), _ptr(dirs), n, _ptr(n_dev), ctypes.byref(grid.desc),
+                                      _ptr(params16[MLP_PARAMS:]), _ptr(params16), _ptr(sig), _ptr(rgb), _ptr(enc),
+                                      _ptr(h), int(rgb_act), vren._stream())
+    vren._ok(st, "ngp_field_forward_act")
     return sig, rgb, enc, h
 
 
@@ -184,18 +195,19 @@ def density_input_grad(xyzs, grid: HashGrid, params16, dL_dsigma=None):
     return out
 
 
-def field_backward(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, grad, n_dev=None, denc_ws=None):
-    """Accumulates dL/dparams (fp32, params layout) into `grad`."""
+def field_backward(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, grad, n_dev=None, denc_ws=None,
+                   rgb_act=0):
+    """Accumulates dL/dparams (fp32, params layout) into `grad` (rgb_act: the forward's colour mode)."""
     n = xyzs.shape[0]
     _check(grad, "grad", torch.float32, grid.n_params)
     _check(enc, "enc", torch.float16)
     _check(dL_dsig, "dL_dsigmas", torch.float32); _check(dL_drgb, "dL_drgbs", torch.float32)
     if denc_ws is None:
         denc_ws = torch.empty(n, 32, device=xyzs.device)
-    st = _lib().ngp_field_backward(_ptr(xyzs), _ptr(dirs), n, _ptr(n_dev), ctypes.byref(grid.desc), _ptr(enc),
-                                   _ptr(params16), _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc_ws), _ptr(grad),
-                                   _ptr(grad[MLP_PARAMS:]), vren._stream())
-    vren._ok(st, "ngp_field_backward")
+    st = _lib().ngp_field_backward_act(_ptr(xyzs), _ptr(dirs), n, _ptr(n_dev), ctypes.byref(grid.desc), _ptr(enc),
+                                       _ptr(params16), _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc_ws), _ptr(grad),
+                                       _ptr(grad[MLP_PARAMS:]), int(rgb_act), vren._stream())
+    vren._ok(st, "ngp_field_backward_act")
 
 
 BIN_LEVEL_LO, BIN_MERGE_HI = 8, 11  # the trainer's hybrid split on object scenes (trainer.NGPTrainer)
@@ -225,7 +237,7 @@ def _rep_buffer(grid, device):
     return rep
 
 
-def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, grad):
+def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, grad, rgb_act=0):
     """field_backward over the samples that carry gradient only, with the
     training step's hybrid hash backward: the rows with a nonzero dL/dsigma or
     dL/drgb are listed on the device (ngp_gradient_rows: no host sync) -- the
@@ -246,8 +258,9 @@ def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL
     cnt = torch.empty(1, dtype=torch.int64, device=dev)
     vren._ok(vren.lib().ngp_gradient_rows(_ptr(dL_dsig), _ptr(dL_drgb), n, _ptr(idx), _ptr(cnt), s), "gradient_rows")
     denc = torch.empty(n, 32, device=dev)
-    vren._ok(L.ngp_field_backward_mlp(_ptr(dirs), n, _ptr(cnt), _ptr(idx), _ptr(enc), 0, _ptr(params16),
-                                      _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc), _ptr(grad), s), "field_backward_mlp")
+    vren._ok(L.ngp_field_backward_mlp_act(_ptr(dirs), n, _ptr(cnt), _ptr(idx), _ptr(enc), 0, _ptr(params16),
+                                          _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc), _ptr(grad), int(rgb_act), s),
+             "field_backward_mlp_act")
     gt = grad[MLP_PARAMS:]
     vren._ok(L.ngp_hash_backward_levels_rep(_ptr(xyzs), n, _ptr(cnt), _ptr(idx), ctypes.byref(grid.desc), _ptr(denc),
                                             _ptr(gt), 0, BIN_LEVEL_LO, _ptr(_rep_buffer(grid, dev)),
@@ -275,11 +288,12 @@ class FP16Shadow:
 
 class _FieldFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xyzs, dirs, params, grid, shadow):
+    def forward(ctx, xyzs, dirs, params, grid, shadow, rgb_act=0):
         p16 = shadow.get()
-        sig, rgb, enc, _ = field_forward(xyzs.contiguous(), dirs.contiguous(), grid, p16, save_enc=True)
+        sig, rgb, enc, _ = field_forward(xyzs.contiguous(), dirs.contiguous(), grid, p16, save_enc=True,
+                                         rgb_act=rgb_act)
         ctx.save_for_backward(xyzs, dirs, enc)
-        ctx.grid, ctx.p16 = grid, p16
+        ctx.grid, ctx.p16, ctx.rgb_act = grid, p16, rgb_act
         return sig, rgb
 
     @staticmethod
@@ -289,10 +303,11 @@ class _FieldFn(torch.autograd.Function):
         dsig = torch.zeros(xyzs.shape[0], device=xyzs.device) if dsig is None else dsig.float().contiguous()
         drgb = torch.zeros(xyzs.shape[0], 3, device=xyzs.device) if drgb is None else drgb.float().contiguous()
         grad = torch.zeros(grid.n_params, device=xyzs.device)
-        field_backward_sparse(xyzs.contiguous(), dirs.contiguous(), grid, ctx.p16, enc, dsig, drgb, grad)
-        return None, None, grad, None, None
+        field_backward_sparse(xyzs.contiguous(), dirs.contiguous(), grid, ctx.p16, enc, dsig, drgb, grad,
+                              rgb_act=ctx.rgb_act)
+        return None, None, grad, None, None, None
 
 
-def field(xyzs, dirs, params, grid, shadow):
+def field(xyzs, dirs, params, grid, shadow, rgb_act=0):
     """Differentiable (w.r.t. params) fused field: -> sigmas (n), rgbs (n,3)."""
-    return _FieldFn.apply(xyzs, dirs, params, grid, shadow)
+    return _FieldFn.apply(xyzs, dirs, params, grid, shadow, rgb_act)

@@ -49,8 +49,11 @@ class NGP(nn.Module):
 
     def __init__(self, scale, rgb_act='Sigmoid', use_raw_HDR=False, seed=4):
         super().__init__()
-        if rgb_act != 'Sigmoid' or use_raw_HDR:
-            raise NotImplementedError("HDR / exposure tonemapper branch (networks.py:80-93) is out of scope")
+        if rgb_act not in ('Sigmoid', 'None'):
+            raise NotImplementedError(f"rgb_act={rgb_act!r}: the reference builds 'Sigmoid' or 'None' (networks.py:68-78)")
+        if rgb_act == 'None' and not use_raw_HDR:
+            raise NotImplementedError("rgb_act='None' without use_raw_HDR needs the exposure tonemapper nets "
+                                      "(networks.py:80-93, 110-131), which are out of scope")
         self.rgb_act = rgb_act
         self.use_raw_HDR = use_raw_HDR
         self.scale = scale
@@ -94,12 +97,23 @@ class NGP(nn.Module):
             sig, h = HG.density_forward(x, self.grid, self._shadow.get(), want_h=return_feat)
         return (sig, h) if return_feat else sig
 
+    def rgb_mode(self, output_radiance=False):
+        """The kernels' colour-output mode (HG.RGB_*) of a forward call: a raw-HDR
+        model (rgb_act='None', use_raw_HDR) has no output activation and
+        applies leaky_relu, or relu with output_radiance (networks.py:152-157);
+        on a sigmoid model use_raw_HDR's leaky_relu is the identity."""
+        if self.rgb_act == 'Sigmoid':
+            return HG.RGB_SIGMOID
+        return HG.RGB_RELU if output_radiance else HG.RGB_LEAKY_RELU
+
     def forward(self, x, d, **kwargs):
-        """networks.py:133-165 (Sigmoid rgb branch) -> sigmas (N) f32, rgbs (N,3) f32."""
+        """networks.py:133-165 -> sigmas (N) f32, rgbs (N,3) f32 (Sigmoid, or the
+        raw-HDR branch: leaky_relu / relu with output_radiance=True)."""
         x, d = x.float().contiguous(), d.float().contiguous()
+        act = self.rgb_mode(kwargs.get('output_radiance', False))
         if torch.is_grad_enabled() and self.params.requires_grad:
-            return HG.field(x, d, self.params, self.grid, self._shadow)
-        sig, rgb, _, _ = HG.field_forward(x, d, self.grid, self._shadow.get(), save_enc=False)
+            return HG.field(x, d, self.params, self.grid, self._shadow, act)
+        sig, rgb, _, _ = HG.field_forward(x, d, self.grid, self._shadow.get(), save_enc=False, rgb_act=act)
         return sig, rgb
 
     # ---------------------------------------------------- occupancy grid

@@ -66,11 +66,12 @@ def _background(kwargs, rays_d, default):
     return default
 
 
-def _test_renderer(model, n_rays, esf, T_threshold, max_samples):
-    """TestRenderer cached on the model per (rays, loop settings, bitfield)."""
+def _test_renderer(model, n_rays, esf, T_threshold, max_samples, rgb_act=0):
+    """TestRenderer cached on the model per (rays, loop settings, bitfield,
+    colour mode: the mode is baked into the captured graphs)."""
     import renderer as RD
     cache = model.__dict__.setdefault('_test_renderers', {})
-    key = (n_rays, float(esf), float(T_threshold), int(max_samples), model.density_bitfield.data_ptr())
+    key = (n_rays, float(esf), float(T_threshold), int(max_samples), model.density_bitfield.data_ptr(), int(rgb_act))
     rr = cache.get(key)
     p16 = model._shadow.get()
     if rr is None:
@@ -78,7 +79,7 @@ def _test_renderer(model, n_rays, esf, T_threshold, max_samples):
             cache.clear()
         rr = RD.TestRenderer(n_rays, model.grid, p16.clone(), model.density_bitfield, model.cascades, model.scale,
                              model.grid_size, exp_step_factor=esf, T_threshold=T_threshold, max_samples=max_samples,
-                             iters_per_graph=16, iters_tail=8)
+                             iters_per_graph=16, iters_tail=8, rgb_act=int(rgb_act))
         rr._src = None
         cache[key] = rr
     if rr._src is not p16:  # parameters changed since the last frame: refresh the renderer's copy
@@ -97,7 +98,8 @@ def __render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
     exp_step_factor = kwargs.get('exp_step_factor', 0.)
     if kwargs.get('device_loop', True) and hasattr(model, '_shadow') and rays_o.is_cuda and len(rays_o) > 0:
         rr = _test_renderer(model, len(rays_o), exp_step_factor, kwargs.get('T_threshold', 1e-4),
-                            kwargs.get('max_samples', MAX_SAMPLES))
+                            kwargs.get('max_samples', MAX_SAMPLES),
+                            model.rgb_mode(kwargs.get('output_radiance', False)))
         # SH_bkg: blended by the frame's closing launch (ngp_render_test_finish_sh)
         bg_sh = _sh_light(kwargs, rays_o.device)
         out = rr.render(rays_o, rays_d, hits_t[:, 0], bg_sh=bg_sh)

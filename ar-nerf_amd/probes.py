@@ -106,7 +106,9 @@ def sh_probes(model, pts, dirs=None, n_rays=2048, SH_bkg=None, blend_bkg=True, p
     dirs: one shared (R,3) set of directions, (P,R,3) per probe, or None for
     get_sphere_rays(P, n_rays).  SH_bkg: a (9,3) global light blended in behind
     the rays (clamped at zero) unless blend_bkg is False.  render_kwargs:
-    T_threshold, max_samples, exp_step_factor, as render() takes them.
+    T_threshold, max_samples, exp_step_factor, output_radiance, as render()
+    takes them (output_radiance: a raw-HDR model's relu radiance, what
+    generate_SH_probes asks for under use_EXR).
 
     Returns {'rgb_sh': (P,9,3), 'trans_sh': (P,9,1)}: the projections of the
     radiance and of 1 - opacity; with return_rays also 'rgb' (P,R,3),
@@ -123,7 +125,7 @@ def sh_probes(model, pts, dirs=None, n_rays=2048, SH_bkg=None, blend_bkg=True, p
     still alive, so a probe's rays are NOT independent of the batch they are
     rendered in: another probes_per_batch gives slightly different values.
     """
-    unknown = set(render_kwargs) - {'T_threshold', 'max_samples', 'exp_step_factor'}
+    unknown = set(render_kwargs) - {'T_threshold', 'max_samples', 'exp_step_factor', 'output_radiance'}
     if unknown:
         raise TypeError(f"sh_probes: unexpected arguments {sorted(unknown)}")
     if not hasattr(model, '_shadow'):
@@ -151,7 +153,8 @@ def sh_probes(model, pts, dirs=None, n_rays=2048, SH_bkg=None, blend_bkg=True, p
     if SH_bkg is not None and blend_bkg:
         bg_sh = torch.as_tensor(SH_bkg, dtype=torch.float32, device=dev).reshape(9, 3).contiguous()
     rr = RND._test_renderer(model, B * R, render_kwargs.get('exp_step_factor', 0.),
-                            render_kwargs.get('T_threshold', 1e-4), render_kwargs.get('max_samples', RND.MAX_SAMPLES))
+                            render_kwargs.get('T_threshold', 1e-4), render_kwargs.get('max_samples', RND.MAX_SAMPLES),
+                            model.rgb_mode(render_kwargs.get('output_radiance', False)))
     rgb_sh = torch.empty(n_batches * B, 9, 3, device=dev)
     trans_sh = torch.empty(n_batches * B, 9, device=dev)
     rays = {'rgb': [], 'opacity': []}

@@ -46,10 +46,13 @@ class TestRenderer:
 
     def __init__(self, n_rays, grid: HG.HashGrid, params16, density_bitfield, cascades, scale, grid_size=128,
                  exp_step_factor=0.0, T_threshold=1e-4, max_samples=MAX_SAMPLES, iters_per_graph=16,
-                 bg_rgb=(0.0, 0.0, 0.0), use_graphs=True, iters_tail=None):
+                 bg_rgb=(0.0, 0.0, 0.0), use_graphs=True, iters_tail=None, rgb_act=0):
         iters_tail = iters_per_graph if iters_tail is None else iters_tail
         if min(iters_per_graph, iters_tail) < 2 or iters_per_graph % 2 or iters_tail % 2:
             raise ValueError("iters_per_graph / iters_tail must be even (alive lists alternate per iteration)")
+        if int(rgb_act) not in (HG.RGB_SIGMOID, HG.RGB_NONE, HG.RGB_LEAKY_RELU, HG.RGB_RELU):
+            raise ValueError(f"rgb_act must be one of hashgrid.RGB_*, got {rgb_act}")
+        self.rgb_act = int(rgb_act)  # colour-output mode of the field (baked into the captured graphs)
         dev = params16.device
         vren._check("params16", params16, torch.float16)
         vren._check("density_bitfield", density_bitfield, torch.uint8)
@@ -101,10 +104,11 @@ class TestRenderer:
                                          _p(self.sample_idx), s), "render_test_march")
         # model(xyzs[valid], dirs[valid]) (rendering.py:204-218): NGP.forward over the list
         # (encode + MLPs in one launch; no encoding kept: nothing goes backward)
-        vren._ok(L.ngp_field_encode_mlp(_p(self.xyzs), _p(self.dirs), self.cap, self.n_valid_ptr, _p(self.sample_idx),
-                                        ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
-                                        _p(self.params16), None, _p(self.sigmas), _p(self.rgbs), None, s),
-                 "field_encode_mlp")
+        vren._ok(L.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, self.n_valid_ptr,
+                                            _p(self.sample_idx), ctypes.byref(self.grid.desc),
+                                            _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), None,
+                                            _p(self.sigmas), _p(self.rgbs), None, self.rgb_act, s),
+                 "field_encode_mlp_act")
         vren._ok(L.ngp_render_test_composite(_p(self.sigmas), _p(self.rgbs), _p(self.deltas), _p(self.ts),
                                              _p(self.n_eff), self.n_rays, par, _p(self.state), _p(self.alive[par]),
                                              _p(self.alive[par ^ 1]), c_float(self.T_threshold), _p(self.opacity),
@@ -195,7 +199,9 @@ class TestRenderer:
         return self.render_loaded()
 
 
-def for_model(model, n_rays, **kwargs):
-    """TestRenderer over a models.networks.NGP (its fp16 shadow and bitfield)."""
+def for_model(model, n_rays, output_radiance=False, **kwargs):
+    """TestRenderer over a models.networks.NGP (its fp16 shadow and bitfield;
+    the model's colour mode, relu for a raw-HDR model with output_radiance)."""
+    kwargs.setdefault('rgb_act', model.rgb_mode(output_radiance))
     return TestRenderer(n_rays, model.grid, model._shadow.get(), model.density_bitfield, model.cascades,
                         model.scale, model.grid_size, **kwargs)

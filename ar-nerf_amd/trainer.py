@@ -48,8 +48,13 @@ class NGPTrainer:
                  update_interval=16, warmup_steps=256, max_samples=MAX_SAMPLES, sample_capacity=None, seed=4,
                  device="cuda", process_group=None, hash_backward="hybrid", bin_samples_per_ray=None, bin_level_lo=None,
                  chunk_first=64, erode=False, lambda_distortion=0.0, bin_merge_hi=None, fused_adam=True, use_graphs=True,
-                 pair_steps=False, emulate_dp=False, dp_fine_buckets=2):
+                 pair_steps=False, emulate_dp=False, dp_fine_buckets=2, use_raw_HDR=False):
         self.dev = torch.device(device)
+        # raw-HDR model (train.py:76-77: NGP(rgb_act='None', use_raw_HDR=True) under --use_EXR): no
+        # colour activation but leaky_relu in training, relu for output_radiance
+        # (networks.py:152-157); fp32 ground truth may exceed 1
+        self.use_raw_HDR = bool(use_raw_HDR)
+        self.rgb_act = HG.RGB_LEAKY_RELU if self.use_raw_HDR else HG.RGB_SIGMOID
         self.scale = float(scale)
         self.batch_size = batch_size
         self.lr0, self.num_epochs, self.steps_per_epoch = lr, num_epochs, steps_per_epoch
@@ -1028,13 +1033,11 @@ class NGPTrainer:
             m = self.msets[self.cur]
             pre = 8 if m["pre_ready"] else 0
             m["pre_ready"] = False
-            vren._ok(HGL.ngp_field_forward_first_pre(_p(self.xyzs), _p(self.dirs), _p(self.deltas), _p(self.rays_a),
-                                                     _p(self.rows_ne), _p(self.n_rows_ne), R, self.cap,
-                                                     ctypes_float(1e-4), HG.ctypes.byref(self.grid.desc),
-                                                     _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
-                                                     _p(self.enc), _p(self.sigmas), _p(self.rgbs), None,
-                                                     _p(self.eval_idx), _p(self.eval_total2), _p(self.eval_stats),
-                                                     pre, s), "field_forward_first")
+            vren._ok(HGL.ngp_field_forward_first_pre_act(
+                _p(self.xyzs), _p(self.dirs), _p(self.deltas), _p(self.rays_a), _p(self.rows_ne), _p(self.n_rows_ne),
+                R, self.cap, ctypes_float(1e-4), HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
+                _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs), None, _p(self.eval_idx),
+                _p(self.eval_total2), _p(self.eval_stats), pre, self.rgb_act, s), "field_forward_first")
             self._ev("hash_encode", 1)
             if fork is not None and at == "r1":
                 # (captured before round 2: round 2 captured first and the march forked from an event
@@ -1064,10 +1067,10 @@ class NGPTrainer:
             self._field_indexed(s)
         else:  # encode + MLPs in one launch over every marched sample
             self._ev("hash_encode", 0)
-            vren._ok(HGL.ngp_field_encode_mlp(_p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_samples), None,
-                                              HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
-                                              _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs), None,
-                                              s), "field_encode_mlp")
+            vren._ok(HGL.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_samples), None,
+                                                  HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
+                                                  _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs),
+                                                  None, self.rgb_act, s), "field_encode_mlp")
             self._ev("hash_encode", 1)
         self._ev("field_fwd", 1)
         if fork is not None and at == "fwd":
@@ -1119,9 +1122,10 @@ class NGPTrainer:
             seg_done = torch.cuda.Event()
             seg_done.record(cs)
         self._ev("mlp_bwd", 0)
-        vren._ok(HGL.ngp_field_backward_mlp(_p(self.dirs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
-                                            _p(self.enc), self.cap, _p(self.params16), _p(self.dsig), _p(self.drgb),
-                                            _p(self.denc), _p(self.grad), s), "field_backward_mlp")
+        vren._ok(HGL.ngp_field_backward_mlp_act(_p(self.dirs), self.cap, _p(self.n_active_total),
+                                                _p(self.sample_idx), _p(self.enc), self.cap, _p(self.params16),
+                                                _p(self.dsig), _p(self.drgb), _p(self.denc), _p(self.grad),
+                                                self.rgb_act, s), "field_backward_mlp")
         self._ev("mlp_bwd", 1)
         if seg_done is not None:
             planned = plan(seg_done)
@@ -1296,16 +1300,20 @@ class NGPTrainer:
         idx = self.eval_idx if idx is None else idx
         total = self.eval_total if total is None else total
         self._ev("hash_encode", 0)
-        vren._ok(HG._lib().ngp_field_encode_mlp(_p(self.xyzs), _p(self.dirs), self.cap, _p(total),
-                                                _p(idx), HG.ctypes.byref(self.grid.desc),
-                                                _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), _p(self.enc),
-                                                _p(self.sigmas), _p(self.rgbs), None, s), "field_encode_mlp")
+        vren._ok(HG._lib().ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(total),
+                                                    _p(idx), HG.ctypes.byref(self.grid.desc),
+                                                    _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
+                                                    _p(self.enc), _p(self.sigmas), _p(self.rgbs), None,
+                                                    self.rgb_act, s), "field_encode_mlp")
         self._ev("hash_encode", 1)
 
     # ---------------------------------------------------- test-time render
     @torch.no_grad()
-    def render(self, rays_o, rays_d, T_threshold=1e-4, max_samples=MAX_SAMPLES, bg=0.0):
-        """__render_rays_test (models/rendering.py:162-253) on the native kernels."""
+    def render(self, rays_o, rays_d, T_threshold=1e-4, max_samples=MAX_SAMPLES, bg=0.0, output_radiance=False):
+        """__render_rays_test (models/rendering.py:162-253) on the native kernels.
+        output_radiance: a raw-HDR trainer's relu radiance instead of the
+        training-time leaky_relu (networks.py:152-157); no effect on a sigmoid one."""
+        act = HG.RGB_RELU if self.use_raw_HDR and output_radiance else self.rgb_act
         N_rays = rays_o.shape[0]
         dev = self.dev
         _, hits_t, _ = vren.ray_aabb_intersect(rays_o, rays_d, self.center, self.half_size, 1)
@@ -1336,7 +1344,7 @@ class NGPTrainer:
             sig = torch.zeros(len(xyzs), device=dev)
             rgbs = torch.zeros(len(xyzs), 3, device=dev)
             sv, rv, _, _ = HG.field_forward(xyzs[valid].contiguous(), dirs[valid].contiguous(), self.grid,
-                                            self.params16, save_enc=False)
+                                            self.params16, save_enc=False, rgb_act=act)
             sig[valid] = sv
             rgbs[valid] = rv
             vren.composite_test_fw(sig.view(-1, Ns), rgbs.view(-1, Ns, 3), deltas, ts, ht, alive, T_threshold, neff,

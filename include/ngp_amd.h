@@ -467,6 +467,68 @@ int ngp_field_backward_mlp(const float* dirs, int64_t n, const int64_t* n_dev, c
 int ngp_hash_backward(const float* xyzs, int64_t n, const int64_t* n_dev, const int32_t* sample_idx,
                       const ngp_hashgrid_t* grid, const float* denc, float* grad_table, void* stream);
 
+/* ---- colour-output modes (raw-HDR models) ------------------------------
+ * The reference's rgb_net has no output activation when the model is built
+ * with rgb_act='None' (models/networks.py:68-78); in raw-HDR mode NGP.forward
+ * then applies F.leaky_relu to the fp16 colour in training and torch.relu
+ * with output_radiance (networks.py:152-157).  With o the fp16 output row of
+ * the colour net (rows 0..2) and g the upstream gradient (fp32):
+ *
+ *   mode                   rgb (f32 holding an fp16 value)           dL/do
+ *   NGP_RGB_SIGMOID    0   sigmoid(o)                                g y (1 - y)
+ *   NGP_RGB_NONE       1   o                                         g
+ *   NGP_RGB_LEAKY_RELU 2   o > 0 ? o : half(float(o) * 0.01f)        o > 0 ? g : g * 0.01f
+ *   NGP_RGB_RELU       3   o > 0 ? o : 0                             o > 0 ? g : 0
+ *
+ * (mode 2 is what torch computes for F.leaky_relu on a half tensor: fp32
+ * opmath, slope 0.01 as fp32, one rounding to half; o == 0 takes the slope
+ * branch in both directions, as in torch.)
+ *
+ * Each _act function below is its base function with one more argument,
+ * int rgb_act, directly before stream; the base function is the _act one with
+ * NGP_RGB_SIGMOID.  PRECEDENCE: a mode outside 0..3 returns NGP_EINVAL before
+ * any other argument is examined and before any launch -- also with n == 0 or
+ * null pointers.  The mode is ignored when the call has no colour output
+ * (dirs == rgbs == NULL).  Everything but the colour value / its gradient is
+ * bit-identical across modes.  ngp_field_mlp_forward, ngp_field_forward_indexed
+ * and ngp_field_forward_first stay sigmoid-only. */
+#define NGP_RGB_SIGMOID 0
+#define NGP_RGB_NONE 1
+#define NGP_RGB_LEAKY_RELU 2
+#define NGP_RGB_RELU 3
+
+/* ngp_field_forward with the colour mode rgb_act (networks.py:68-78, 152-157). */
+int ngp_field_forward_act(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                          const ngp_hashgrid_t* grid, const void* table_f16, const void* mlp_f16,
+                          float* sigmas, float* rgbs, void* enc_f16, void* h_f16, int rgb_act, void* stream);
+/* ngp_field_encode_mlp with the colour mode rgb_act (networks.py:68-78,
+ * 152-157); dirs == rgbs == NULL: density net only, the mode is unused. */
+int ngp_field_encode_mlp_act(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                             const int32_t* sample_idx, const ngp_hashgrid_t* grid, const void* table_f16,
+                             const void* mlp_f16, void* enc_pm, float* sigmas, float* rgbs, void* h_f16,
+                             int rgb_act, void* stream);
+/* ngp_field_forward_first_pre with the colour mode rgb_act (networks.py:68-78,
+ * 152-157): round 1 of a raw-HDR training step.  The transmittance / round-2
+ * outputs do not depend on the mode. */
+int ngp_field_forward_first_pre_act(const float* xyzs, const float* dirs, const float* deltas,
+                                    const int64_t* rays_a, const int32_t* rows, const int64_t* n_rows_dev,
+                                    int64_t n_rows, int64_t n, float T_threshold, const ngp_hashgrid_t* grid,
+                                    const void* table_f16, const void* mlp_f16, void* enc_pm, float* sigmas,
+                                    float* rgbs, int32_t* rest, int32_t* list2, int64_t* total2,
+                                    int64_t* evaluated, int pre_levels, int rgb_act, void* stream);
+/* ngp_field_backward for a forward run in mode rgb_act (networks.py:68-78,
+ * 152-157): dL/do as tabulated above, the rest of the backward unchanged. */
+int ngp_field_backward_act(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                           const ngp_hashgrid_t* grid, const void* enc_f16, const void* mlp_f16,
+                           const float* dL_dsigmas, const float* dL_drgbs, float* denc_ws, float* grad_mlp,
+                           float* grad_table, int rgb_act, void* stream);
+/* ngp_field_backward_mlp for a forward run in mode rgb_act (networks.py:68-78,
+ * 152-157). */
+int ngp_field_backward_mlp_act(const float* dirs, int64_t n, const int64_t* n_dev, const int32_t* sample_idx,
+                               const void* enc_f16, int64_t enc_pm_stride, const void* mlp_f16,
+                               const float* dL_dsigmas, const float* dL_drgbs, float* denc_ws, float* grad_mlp,
+                               int rgb_act, void* stream);
+
 /* Binned form of ngp_hash_backward (same gradient up to fp32 summation order):
  * records per (level, 16384-entry range) are staged in `workspace`, then each
  * range is summed in LDS and written once -- no per-sample global atomics

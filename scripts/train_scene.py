@@ -34,6 +34,10 @@ def main(argv=None):
                     help="exact mode: every marched sample through the field (chunk_first=0) and the per-sample "
                          "atomic hash backward, instead of the chunked field + binned fine-level backward")
     ap.add_argument("--seed", type=int, default=4)
+    ap.add_argument("--use_raw_HDR", action="store_true",
+                    help="raw-HDR model (train.py:76-77 under --use_EXR): no colour activation, leaky_relu in "
+                         "training, evaluated with output_radiance=True and without the [0,1] clamp; needs fp32 "
+                         "ground truth")
     ap.add_argument("--sync-every", type=int, default=0, help="(diagnostics) synchronize + report every N steps")
     a = ap.parse_args(argv)
     from datasets import dataset_dict
@@ -42,12 +46,15 @@ def main(argv=None):
     torch.cuda.set_device(dev)
     train = dataset_dict[a.dataset](a.root, split='train', downsample=a.downsample)
     test = dataset_dict[a.dataset](a.root, split='test', downsample=a.downsample)
+    if a.use_raw_HDR and not torch.as_tensor(train.rays).is_floating_point():
+        raise SystemExit(f"--use_raw_HDR needs floating-point (fp32) ground truth; dataset {a.dataset!r} at {a.root} "
+                         f"holds {torch.as_tensor(train.rays).dtype} pixels only")
     gt = train.gt_f32().to(dev)  # float targets, as the reference's loss sees them
     dirs, poses = train.directions.to(dev).contiguous(), train.poses.to(dev).contiguous()
     # erode for COLMAP scenes, as train.py:176-178 passes erode=dataset_name=='colmap'
     mode = dict(chunk_first=0, hash_backward="atomic") if a.exact else {}
     tr = NGPTrainer(scale=a.scale, batch_size=a.batch, device=dev, num_epochs=max(1, a.steps // 1000),
-                    erode=a.dataset == "colmap", seed=a.seed, **mode)
+                    erode=a.dataset == "colmap", seed=a.seed, use_raw_HDR=a.use_raw_HDR, **mode)
     tr.mark_invisible_cells(train.K.to(dev), poses, train.img_wh)  # train.py:169-172
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -67,11 +74,13 @@ def main(argv=None):
         P = test.poses[i].to(dev)
         d = (tdirs @ P[:, :3].t()).contiguous()
         o = P[:, 3].expand_as(d).contiguous()
-        out = tr.render(o, d, bg=1.0 if tr.esf == 0 else 0.0)
-        mse = torch.mean((out["rgb"].clamp(0, 1) - test.rays[i].to(dev)) ** 2).item()
+        out = tr.render(o, d, bg=1.0 if tr.esf == 0 else 0.0, output_radiance=a.use_raw_HDR)
+        pred = out["rgb"] if a.use_raw_HDR else out["rgb"].clamp(0, 1)  # (radiance is not clamped to [0,1])
+        mse = torch.mean((pred - test.rays[i].to(dev)[..., :3].float()) ** 2).item()
         psnrs.append(-10 * math.log10(max(mse, 1e-12)))
     import vren
     res = {"dataset": a.dataset, "root": a.root, "steps": a.steps, "mode": "exact" if a.exact else "default",
+           "use_raw_HDR": bool(a.use_raw_HDR),
            "guard_hits": int(vren.lib().ngp_guard_hits()),
            "train_rays_per_s": round(a.steps * a.batch / t_train, 1),
            "test_psnr": round(sum(psnrs) / max(1, len(psnrs)), 3), "test_views": n}
