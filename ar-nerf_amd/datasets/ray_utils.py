@@ -36,6 +36,23 @@ def get_rays(directions, c2w):
     return rays_o, rays_d
 
 
+def axisangle_to_R(v):
+    """ray_utils.py:74-100 (Rodrigues, from nerfmm's lie_group_helper): axis-angle v (3) or (B,3) ->
+    R (3,3) or (B,3,3) = I + sin(t)/t K + (1 - cos(t))/t^2 K^2, t = |v| + 1e-7 (the reference's guard:
+    finite value and gradient at v = 0), K the skew matrix of v.  fp32 under autocast."""
+    with torch.autocast(device_type=v.device.type, enabled=False):
+        single = v.ndim == 1
+        v = (v[None] if single else v).float()
+        zero = torch.zeros_like(v[:, :1])
+        skew_v = torch.stack([torch.cat([zero, -v[:, 2:3], v[:, 1:2]], 1),
+                              torch.cat([v[:, 2:3], zero, -v[:, 0:1]], 1),
+                              torch.cat([-v[:, 1:2], v[:, 0:1], zero], 1)], dim=1)  # (B,3,3)
+        norm_v = (torch.norm(v, dim=1) + 1e-7)[:, None, None]
+        eye = torch.eye(3, device=v.device)
+        R = eye + (torch.sin(norm_v) / norm_v) * skew_v + ((1 - torch.cos(norm_v)) / norm_v ** 2) * (skew_v @ skew_v)
+        return R[0] if single else R
+
+
 def normalize(v):
     return v / np.linalg.norm(v)
 

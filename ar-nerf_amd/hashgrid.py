@@ -45,6 +45,7 @@ def _lib():
         L.ngp_field_forward.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, vp]
         L.ngp_density_forward.argtypes = [vp, c_int64, vp, P, vp, vp, vp, vp, vp]
         L.ngp_density_input_grad.argtypes = [vp, c_int64, P, vp, vp, vp, vp, vp]
+        L.ngp_field_input_grad.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, vp, vp, c_int, vp, vp, vp]
         L.ngp_field_backward.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, vp, vp]
         L.ngp_field_backward_mlp.argtypes = [vp, c_int64, vp, vp, vp, c_int64, vp, vp, vp, vp, vp, vp]
         L.ngp_hash_encode.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp]
@@ -88,7 +89,8 @@ def _lib():
                   L.ngp_hash_binned_plan, L.ngp_hash_binned_apply, L.ngp_hash_binned_write,
                   L.ngp_hash_binned_accum, L.ngp_hash_binned_accum_levels, L.ngp_hash_binned_apply_adam,
                   L.ngp_hash_binned_accum_adam, L.ngp_field_forward_act, L.ngp_field_backward_act,
-                  L.ngp_field_backward_mlp_act, L.ngp_field_encode_mlp_act, L.ngp_field_forward_first_pre_act):
+                  L.ngp_field_backward_mlp_act, L.ngp_field_encode_mlp_act, L.ngp_field_forward_first_pre_act,
+                  L.ngp_field_input_grad):
             f.restype = c_int
         _declared = True
     return L
@@ -195,6 +197,39 @@ def density_input_grad(xyzs, grid: HashGrid, params16, dL_dsigma=None):
     return out
 
 
+def field_input_grad(xyzs, dirs, grid: HashGrid, params16, enc, dL_drgb, denc, rgb_act=0, n_dev=None,
+                     sample_idx=None, want_dirs=True):
+    """Input gradients of field_forward over the listed rows (sample_idx (n) i32 with the count in n_dev,
+    the list of ngp_gradient_rows; None: all rows) -> dL/dxyzs (n,3), dL/ddirs (n,3) | None, zero on the
+    unlisted rows.  denc (n,32) f32: dL/d(encoding) as the MLP backward (ngp_field_backward_mlp_act)
+    wrote it for the same list -- it carries dL/dsigma and the colour path through h.  want_dirs=False:
+    the position part alone (dirs, enc, dL_drgb may be None)."""
+    n = xyzs.shape[0]
+    _check(xyzs, "xyzs", torch.float32)
+    _check(params16, "params16", torch.float16, grid.n_params)
+    _check(denc, "denc", torch.float32)
+    if denc.numel() < 32 * (n if sample_idx is None else sample_idx.numel()):
+        raise RuntimeError("denc must hold 32 floats per listed row")
+    if sample_idx is not None:
+        _check(sample_idx, "sample_idx", torch.int32)
+        if n_dev is None:
+            raise RuntimeError("sample_idx needs its count in n_dev")
+    if want_dirs:
+        _check(dirs, "dirs", torch.float32); _check(enc, "enc", torch.float16); _check(dL_drgb, "dL_drgbs", torch.float32)
+        if dirs.numel() != 3 * n or enc.numel() != 32 * n or dL_drgb.numel() != 3 * n:
+            raise RuntimeError("dirs (n,3), enc (n,32) and dL_drgbs (n,3) must match xyzs (n,3)")
+    dx = torch.zeros(n, 3, device=xyzs.device)
+    dd = torch.zeros(n, 3, device=xyzs.device) if want_dirs else None
+    rows = n if sample_idx is None else sample_idx.numel()
+    st = _lib().ngp_field_input_grad(_ptr(xyzs), _ptr(dirs) if want_dirs else None, rows, _ptr(n_dev),
+                                     _ptr(sample_idx), ctypes.byref(grid.desc), _ptr(params16[MLP_PARAMS:]),
+                                     _ptr(params16), _ptr(enc) if want_dirs else None,
+                                     _ptr(dL_drgb) if want_dirs else None, _ptr(denc), int(rgb_act), _ptr(dx),
+                                     _ptr(dd), vren._stream())
+    vren._ok(st, "ngp_field_input_grad")
+    return dx, dd
+
+
 def field_backward(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, grad, n_dev=None, denc_ws=None,
                    rgb_act=0):
     """Accumulates dL/dparams (fp32, params layout) into `grad` (rgb_act: the forward's colour mode)."""
@@ -237,7 +272,8 @@ def _rep_buffer(grid, device):
     return rep
 
 
-def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, grad, rgb_act=0):
+def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, grad, rgb_act=0,
+                          want_xyzs=False, want_dirs=False):
     """field_backward over the samples that carry gradient only, with the
     training step's hybrid hash backward: the rows with a nonzero dL/dsigma or
     dL/drgb are listed on the device (ngp_gradient_rows: no host sync) -- the
@@ -245,13 +281,25 @@ def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL
     exact zero, and a zero row adds exactly nothing -- then the MLP backward,
     the atomic coarse levels [0, 8) (levels 0-3 into 8 gradient replicas, folded
     after) and the binned levels [8, 16) over that list
-    (the same gradient as field_backward up to fp32 summation order)."""
+    (the same gradient as field_backward up to fp32 summation order).
+    want_xyzs / want_dirs: also -> (dL/dxyzs | None, dL/ddirs | None) over the same list
+    (field_input_grad, after the MLP backward has written dL/denc).  grad None: frozen
+    parameters -- the MLP backward still runs for dL/denc, its dW goes to a throwaway
+    buffer, and the hash backward is skipped."""
     n = xyzs.shape[0]
-    _check(grad, "grad", torch.float32, grid.n_params)
+    want_in = want_xyzs or want_dirs
+    if grad is None:
+        if not want_in:
+            return None, None
+        mlp_grad = torch.zeros(MLP_PARAMS, device=xyzs.device)
+    else:
+        _check(grad, "grad", torch.float32, grid.n_params)
+        mlp_grad = grad
     _check(enc, "enc", torch.float16)
     _check(dL_dsig, "dL_dsigmas", torch.float32); _check(dL_drgb, "dL_drgbs", torch.float32)
     if n == 0:
-        return
+        z = torch.zeros(0, 3, device=xyzs.device)
+        return (z if want_in else None), (z.clone() if want_dirs else None)
     dev = xyzs.device
     L, s = _lib(), vren._stream()
     idx = torch.empty(n, dtype=torch.int32, device=dev)
@@ -259,8 +307,14 @@ def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL
     vren._ok(vren.lib().ngp_gradient_rows(_ptr(dL_dsig), _ptr(dL_drgb), n, _ptr(idx), _ptr(cnt), s), "gradient_rows")
     denc = torch.empty(n, 32, device=dev)
     vren._ok(L.ngp_field_backward_mlp_act(_ptr(dirs), n, _ptr(cnt), _ptr(idx), _ptr(enc), 0, _ptr(params16),
-                                          _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc), _ptr(grad), int(rgb_act), s),
+                                          _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc), _ptr(mlp_grad), int(rgb_act), s),
              "field_backward_mlp_act")
+    dx = dd = None
+    if want_in:
+        dx, dd = field_input_grad(xyzs, dirs, grid, params16, enc, dL_drgb, denc, rgb_act=rgb_act, n_dev=cnt,
+                                  sample_idx=idx, want_dirs=want_dirs)
+    if grad is None:
+        return dx, dd
     gt = grad[MLP_PARAMS:]
     vren._ok(L.ngp_hash_backward_levels_rep(_ptr(xyzs), n, _ptr(cnt), _ptr(idx), ctypes.byref(grid.desc), _ptr(denc),
                                             _ptr(gt), 0, BIN_LEVEL_LO, _ptr(_rep_buffer(grid, dev)),
@@ -268,6 +322,7 @@ def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL
     vren._ok(L.ngp_hash_backward_binned(_ptr(xyzs), n, _ptr(cnt), _ptr(idx), ctypes.byref(grid.desc), _ptr(denc),
                                         _ptr(gt), _ptr(_binned_workspace(dev)), BIN_WS_SAMPLES, BIN_LEVEL_LO,
                                         BIN_MERGE_HI, s), "hash_backward_binned")
+    return dx, dd
 
 
 class FP16Shadow:
@@ -302,12 +357,14 @@ class _FieldFn(torch.autograd.Function):
         grid = ctx.grid
         dsig = torch.zeros(xyzs.shape[0], device=xyzs.device) if dsig is None else dsig.float().contiguous()
         drgb = torch.zeros(xyzs.shape[0], 3, device=xyzs.device) if drgb is None else drgb.float().contiguous()
-        grad = torch.zeros(grid.n_params, device=xyzs.device)
-        field_backward_sparse(xyzs.contiguous(), dirs.contiguous(), grid, ctx.p16, enc, dsig, drgb, grad,
-                              rgb_act=ctx.rgb_act)
-        return None, None, grad, None, None, None
+        need_x, need_d, need_p = ctx.needs_input_grad[:3]
+        grad = torch.zeros(grid.n_params, device=xyzs.device) if need_p else None
+        dx, dd = field_backward_sparse(xyzs.contiguous(), dirs.contiguous(), grid, ctx.p16, enc, dsig, drgb, grad,
+                                       rgb_act=ctx.rgb_act, want_xyzs=need_x, want_dirs=need_d)
+        return (dx if need_x else None), dd, grad, None, None, None
 
 
 def field(xyzs, dirs, params, grid, shadow, rgb_act=0):
-    """Differentiable (w.r.t. params) fused field: -> sigmas (n), rgbs (n,3)."""
+    """Differentiable fused field (w.r.t. params, and xyzs / dirs where they require grad:
+    pose refinement) -> sigmas (n), rgbs (n,3)."""
     return _FieldFn.apply(xyzs, dirs, params, grid, shadow, rgb_act)

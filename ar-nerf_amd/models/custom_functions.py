@@ -22,7 +22,11 @@ class RayAABBIntersector(torch.autograd.Function):
     @staticmethod
     @custom_fwd(cast_inputs=torch.float32)
     def forward(ctx, rays_o, rays_d, center, half_size, max_hits):
-        return tuple(vren.ray_aabb_intersect(rays_o, rays_d, center, half_size, max_hits))
+        out = tuple(vren.ray_aabb_intersect(rays_o, rays_d, center, half_size, max_hits))
+        # no derivative (the reference defines no backward): with rays that require grad (pose
+        # refinement) the outputs must not join the graph, or autograd calls the missing backward
+        ctx.mark_non_differentiable(*out)
+        return out
 
 
 class RaySphereIntersector(torch.autograd.Function):
@@ -67,8 +71,9 @@ class RayMarcher(torch.autograd.Function):
     @custom_bwd
     def backward(ctx, dL_drays_a, dL_dxyzs, dL_ddirs, dL_ddeltas, dL_dts, dL_dtotal_samples):
         rays_a, ts = ctx.saved_tensors
-        dL_drays_o = _segment_sum(dL_dxyzs, rays_a, ctx.n_rays)
-        dL_drays_d = _segment_sum(dL_dxyzs * ts[:, None] + dL_ddirs, rays_a, ctx.n_rays)
+        # the two segment_csr sums in one launch, without atomics (_segment_sum: the comparison helper)
+        dL_drays_o, dL_drays_d = vren.ray_segment_sum(dL_dxyzs.float().contiguous(), dL_ddirs.float().contiguous(),
+                                                      ts, rays_a, ctx.n_rays)
         return dL_drays_o, dL_drays_d, None, None, None, None, None, None, None
 
 

@@ -111,7 +111,7 @@ class NGP(nn.Module):
         raw-HDR branch: leaky_relu / relu with output_radiance=True)."""
         x, d = x.float().contiguous(), d.float().contiguous()
         act = self.rgb_mode(kwargs.get('output_radiance', False))
-        if torch.is_grad_enabled() and self.params.requires_grad:
+        if torch.is_grad_enabled() and (self.params.requires_grad or x.requires_grad or d.requires_grad):
             return HG.field(x, d, self.params, self.grid, self._shadow, act)
         sig, rgb, _, _ = HG.field_forward(x, d, self.grid, self._shadow.get(), save_enc=False, rgb_act=act)
         return sig, rgb

@@ -77,6 +77,7 @@ def _declare(L):
                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "ngp_active_samples": [vp, vp, c_int64, vp, vp, vp, vp],
         "ngp_gradient_rows": [vp, vp, c_int64, vp, vp, vp],
+        "ngp_ray_segment_sum": [vp, vp, vp, c_int64, vp, c_int64, vp, vp, vp],
         "ngp_nerf_loss_fw": [vp, vp, vp, vp, c_int64, c_int, c_float, c_float, c_float, vp, vp, vp, vp],
         "ngp_nerf_loss_bw": [vp, vp, vp, vp, c_int64, c_int, c_float, c_float, c_float, vp, vp, vp, vp, vp, vp, vp],
         "ngp_chunk_counts": [vp, c_int64, c_int, vp, vp, c_float, vp, vp],
@@ -470,6 +471,27 @@ def composite_train_bw(dL_dopacity, dL_ddepth, dL_drgb, dL_dws, sigmas, rgbs, ws
         _check("rgb", rgb, torch.float32), float(T_threshold), c_void_p(dsig.data_ptr()), c_void_p(drgbs.data_ptr()),
         _stream()), "composite_train_bw")
     return [dsig, drgbs]
+
+
+def ray_segment_sum(dL_dxyzs, dL_ddirs, ts, rays_a, n_rays=None):
+    """RayMarcher.backward's segment sums (custom_functions.py:107-110) -> [dL_drays_o, dL_drays_d] (n_rays,3):
+    per row (ray, start, N) of rays_a, sum dL_dxyzs and sum (ts * dL_dxyzs + dL_ddirs) over the ray's
+    samples (dL_ddirs may be None).  Run-to-run bit-identical (no atomics)."""
+    nr = rays_a.shape[0] if n_rays is None else int(n_rays)
+    if rays_a.shape[0] > nr:
+        raise RuntimeError("rays_a has more rows than n_rays")
+    N = dL_dxyzs.shape[0]
+    if ts.numel() != N or (dL_ddirs is not None and dL_ddirs.numel() != 3 * N):
+        raise RuntimeError("dL_dxyzs (N,3), dL_ddirs (N,3) and ts (N) must agree")
+    dev = dL_dxyzs.device
+    do = torch.zeros(nr, 3, device=dev)
+    dd = torch.zeros(nr, 3, device=dev)
+    _ok(lib().ngp_ray_segment_sum(
+        _check("dL_dxyzs", dL_dxyzs, torch.float32),
+        _check("dL_ddirs", dL_ddirs, torch.float32) if dL_ddirs is not None else None,
+        _check("ts", ts, torch.float32), N, _check("rays_a", rays_a, torch.int64), rays_a.shape[0],
+        c_void_p(do.data_ptr()), c_void_p(dd.data_ptr()), _stream()), "ray_segment_sum")
+    return [do, dd]
 
 
 def composite_test_fw(sigmas, rgbs, deltas, ts, hits_t, alive_indices, T_threshold, N_eff_samples, opacity, depth,

@@ -51,6 +51,7 @@ enum {
     NGP_K_SAMPLE_BATCH = 0, NGP_K_SUMMARY, NGP_K_MARCH, NGP_K_SCAN_RAYS, NGP_K_COMPACT, NGP_K_SEGMENTS,
     NGP_K_HASH_ENCODE, NGP_K_FIELD_MLP, NGP_K_CHUNK, NGP_K_COMPOSITE, NGP_K_HASH_COUNT, NGP_K_HASH_SCAN,
     NGP_K_HASH_PLAN, NGP_K_MLP_BWD, NGP_K_HASH_BWD_COARSE, NGP_K_HASH_WRITE, NGP_K_HASH_ACCUM, NGP_K_ADAM,
+    NGP_K_INPUT_GRAD, NGP_K_RAY_SEGSUM,
     NGP_K_COUNT
 };
 int ngp_timing_set(uint64_t* stamps, const int64_t* step_dev, int64_t ring, int n_ids, int per_id, uint64_t begin_mask,
@@ -362,6 +363,37 @@ int ngp_density_forward(const float* xyzs, int64_t n, const int64_t* n_dev, cons
  * (models/rendering.py:300-313) takes from torch.autograd.grad. */
 int ngp_density_input_grad(const float* xyzs, int64_t n, const ngp_hashgrid_t* grid, const void* table_f16,
                            const void* mlp_f16, const float* dL_dsigma, float* dL_dx, void* stream);
+
+/* Input gradients of NGP.forward (models/networks.py:133-146) over the
+ * gradient-carrying rows (n, n_dev, sample_idx as ngp_field_backward_mlp_act;
+ * the list of ngp_gradient_rows): what tcnn's input gradients of the grid
+ * encoding, the SH encoding and both networks give RayMarcher.backward
+ * (custom_functions.py:102-112).  Runs after ngp_field_backward_mlp_act:
+ * denc (n,32) f32, 16-byte aligned, is the dL/d(encoding) that call wrote,
+ * row j for listed sample sample_idx[j] (it carries dL/dsigma and the colour
+ * path through h).  dL_dxyzs (n_samples,3) f32 receives dL/dx through the
+ * trilinear weights (the encoding's fp16 rounding straight-through).
+ * dL_ddirs (n_samples,3) f32, nullable: dL/dd through the colour net (the
+ * forward recomputed from enc_f16, the forward's saved (n_samples,32) fp16
+ * encoding; gradients fp32 throughout), SH4 and d/|d|; needs dirs, mlp_f16,
+ * enc_f16 and dL_drgbs (n_samples,3).  Only listed rows are written: the
+ * caller zeroes both outputs.  rgb_act: the forward's NGP_RGB_* mode.  tcnn's
+ * own input-gradient arithmetic is not available: parity unpinned. */
+int ngp_field_input_grad(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                         const int32_t* sample_idx, const ngp_hashgrid_t* grid, const void* table_f16,
+                         const void* mlp_f16, const void* enc_f16, const float* dL_drgbs, const float* denc,
+                         int rgb_act, float* dL_dxyzs, float* dL_ddirs, void* stream);
+
+/* RayMarcher.backward's two segment_csr sums (custom_functions.py:107-110): per
+ * row r of rays_a (n_rays,3) i64 = (ray, start, N), over samples [start, start+N):
+ *   dL_drays_o[ray] = sum dL_dxyzs;  dL_drays_d[ray] = sum (ts * dL_dxyzs + dL_ddirs)
+ * (dL_ddirs nullable).  One wave per ray, lanes combined in a fixed butterfly:
+ * bit-identical from run to run.  N = 0 gives zeros; a row whose ray index is
+ * outside [0, n_rays) writes nothing, and a segment outside [0, n_samples] counts
+ * a guard hit and sums nothing. */
+int ngp_ray_segment_sum(const float* dL_dxyzs, const float* dL_ddirs, const float* ts, int64_t n_samples,
+                        const int64_t* rays_a, int64_t n_rays, float* dL_drays_o, float* dL_drays_d,
+                        void* stream);
 
 /* Backward of ngp_field_forward (tcnn's backward for the three modules +
  * TruncExp.backward, custom_functions.py:169-173).  enc_f16 is the forward's
