@@ -41,9 +41,28 @@
 // ray_segment_sum_kernel: one wave per ray; lanes walk the ray's samples with
 // stride 64 and combine in a fixed xor butterfly, so the sums are bit-identical
 // from run to run (custom_functions._segment_sum's index_add_ is atomic).
+//
+// This file is compiled twice: as itself, and from inputgrad_pm.hip with
+// NGP_ENC_PAIR_MAJOR defined, which builds field_input_grad_pm_kernel alone --
+// the same kernel reading the saved encoding in the training step's pair-major
+// layout (field.hip: enc[p][i][0..3] = row i's features 4p..4p+3, row stride
+// enc_pm_stride) behind ngp_field_input_grad_pm.  Two translation units, so the
+// row-major kernel's code is what it was before the second one existed.
 #pragma clang fp contract(off)
 #include "field_net.h"
 #include "grid.h"
+
+#ifdef NGP_ENC_PAIR_MAJOR
+#define NGP_INPUT_GRAD_KERNEL field_input_grad_pm_kernel
+#define NGP_ENC_STRIDE_PARAM , int64_t enc_pm_stride
+#define NGP_ENC_ROW(enc, i, g) \
+    pack(*reinterpret_cast<const h4*>((enc) + ((2 * (g)) * enc_pm_stride + (i)) * 4), \
+         *reinterpret_cast<const h4*>((enc) + ((2 * (g) + 1) * enc_pm_stride + (i)) * 4))
+#else
+#define NGP_INPUT_GRAD_KERNEL field_input_grad_kernel
+#define NGP_ENC_STRIDE_PARAM
+#define NGP_ENC_ROW(enc, i, g) *reinterpret_cast<const h8*>((enc) + (i) * 32 + 8 * (g))
+#endif
 
 namespace ngp {
 
@@ -124,11 +143,11 @@ __device__ __forceinline__ void sh4_grad(float x, float y, float z, const float 
     gu[0] = ax; gu[1] = ay; gu[2] = az;
 }
 
-__global__ void __launch_bounds__(256) field_input_grad_kernel(
+__global__ void __launch_bounds__(256) NGP_INPUT_GRAD_KERNEL(
     const float* __restrict__ xyzs, const float* __restrict__ dirs, int64_t n, const int64_t* __restrict__ n_dev,
     const int32_t* __restrict__ sidx, GridArgs ga, const uint32_t* __restrict__ table,
     const _Float16* __restrict__ mlp, const _Float16* __restrict__ enc, const float* __restrict__ dL_drgb,
-    const float* __restrict__ denc, int act, float* __restrict__ dL_dx, float* __restrict__ dL_dd) {
+    const float* __restrict__ denc, int act, float* __restrict__ dL_dx, float* __restrict__ dL_dd NGP_ENC_STRIDE_PARAM) {
     __shared__ __attribute__((aligned(16))) _Float16 sw[SWF];
     __shared__ LevelLds lv;
     const bool want_d = dL_dd != nullptr;  // (block-uniform)
@@ -162,7 +181,7 @@ __global__ void __launch_bounds__(256) field_input_grad_kernel(
         }
         if (!want_d) continue;
         // ---- direction: the forward again, through the forward's functions
-        const h8 e = valid ? *reinterpret_cast<const h8*>(enc + i * 32 + 8 * g) : h8{0, 0, 0, 0, 0, 0, 0, 0};
+        const h8 e = valid ? NGP_ENC_ROW(enc, i, g) : h8{0, 0, 0, 0, 0, 0, 0, 0};
         h4 h1[4];
         const h4 hh = density_net(e, sw, s, g, h1);
         const float dx = valid ? dirs[3 * i] : 0.f, dy = valid ? dirs[3 * i + 1] : 0.f, dz = valid ? dirs[3 * i + 2] : 1.f;
@@ -258,6 +277,7 @@ __global__ void __launch_bounds__(256) field_input_grad_kernel(
     }
 }
 
+#ifndef NGP_ENC_PAIR_MAJOR
 // Per ray r of rays_a (ray index, start, N): sums over its samples [start, start + N).
 __global__ void __launch_bounds__(256) ray_segment_sum_kernel(const float* __restrict__ dL_dx,
                                                               const float* __restrict__ dL_dd,
@@ -300,10 +320,38 @@ __global__ void __launch_bounds__(256) ray_segment_sum_kernel(const float* __res
     }
 }
 
+#endif  // NGP_ENC_PAIR_MAJOR
+
 }  // namespace ngp
 
 using namespace ngp;
 
+#ifdef NGP_ENC_PAIR_MAJOR
+extern "C" int ngp_field_input_grad_pm(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                                       const int32_t* sample_idx, const ngp_hashgrid_t* grid, const void* table_f16,
+                                       const void* mlp_f16, const void* enc_f16, int64_t enc_pm_stride,
+                                       const float* dL_drgbs, const float* denc, int rgb_act, float* dL_dxyzs,
+                                       float* dL_ddirs, void* stream) {
+    NGP_CHECK_ARG(rgb_act >= NGP_RGB_SIGMOID && rgb_act <= NGP_RGB_RELU);
+    GridArgs ga;
+    int st = grid_args(grid, ga);
+    if (st) return st;
+    NGP_CHECK_ARG(n >= 0 && enc_pm_stride > 0);
+    if (n == 0) return NGP_OK;
+    NGP_CHECK_ARG(n <= INT32_MAX);  // rows are listed as int32
+    NGP_CHECK_ARG(xyzs && table_f16 && denc && dL_dxyzs && ((uintptr_t)denc & 15) == 0);
+    if (dL_ddirs) {
+        NGP_CHECK_ARG(dirs && mlp_f16 && enc_f16 && dL_drgbs);
+        NGP_CHECK_ARG(((uintptr_t)mlp_f16 & 15) == 0 && ((uintptr_t)enc_f16 & 7) == 0);
+    }
+    hipStream_t s = as_stream(stream);
+    static const unsigned cap = resident_blocks(field_input_grad_pm_kernel, 256, 0);
+    NGP_TIMED(NGP_K_INPUT_GRAD, s, field_input_grad_pm_kernel<<<persistent_blocks(n, 64, cap), 256, 0, s>>>(
+        xyzs, dirs, n, n_dev, sample_idx, ga, (const uint32_t*)table_f16, (const _Float16*)mlp_f16,
+        (const _Float16*)enc_f16, dL_drgbs, denc, rgb_act, dL_dxyzs, dL_ddirs, enc_pm_stride));
+    return ngp_launch_status();
+}
+#else
 extern "C" int ngp_field_input_grad(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
                                     const int32_t* sample_idx, const ngp_hashgrid_t* grid, const void* table_f16,
                                     const void* mlp_f16, const void* enc_f16, const float* dL_drgbs,
@@ -340,3 +388,4 @@ extern "C" int ngp_ray_segment_sum(const float* dL_dxyzs, const float* dL_ddirs,
         dL_dxyzs, dL_ddirs, ts, n_samples, rays_a, n_rays, dL_drays_o, dL_drays_d));
     return ngp_launch_status();
 }
+#endif  // NGP_ENC_PAIR_MAJOR

@@ -46,6 +46,7 @@ def _lib():
         L.ngp_density_forward.argtypes = [vp, c_int64, vp, P, vp, vp, vp, vp, vp]
         L.ngp_density_input_grad.argtypes = [vp, c_int64, P, vp, vp, vp, vp, vp]
         L.ngp_field_input_grad.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, vp, vp, c_int, vp, vp, vp]
+        L.ngp_field_input_grad_pm.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, c_int64, vp, vp, c_int, vp, vp, vp]
         L.ngp_field_backward.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, vp, vp]
         L.ngp_field_backward_mlp.argtypes = [vp, c_int64, vp, vp, vp, c_int64, vp, vp, vp, vp, vp, vp]
         L.ngp_hash_encode.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp]
@@ -90,7 +91,7 @@ def _lib():
                   L.ngp_hash_binned_accum, L.ngp_hash_binned_accum_levels, L.ngp_hash_binned_apply_adam,
                   L.ngp_hash_binned_accum_adam, L.ngp_field_forward_act, L.ngp_field_backward_act,
                   L.ngp_field_backward_mlp_act, L.ngp_field_encode_mlp_act, L.ngp_field_forward_first_pre_act,
-                  L.ngp_field_input_grad):
+                  L.ngp_field_input_grad, L.ngp_field_input_grad_pm):
             f.restype = c_int
         _declared = True
     return L

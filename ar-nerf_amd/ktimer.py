@@ -22,7 +22,8 @@ import vren
 
 NAMES = ["sample_batch", "bitfield_summary", "march", "scan_rays", "march_compact", "segments", "hash_encode",
          "field_mlp", "chunk_rest", "composite_loss", "hash_count", "hash_scan", "hash_plan", "mlp_bwd",
-         "hash_bwd_coarse", "hash_write", "hash_accum", "adam", "input_grad", "ray_segment_sum"]  # include/ngp_amd.h NGP_K_* order
+         "hash_bwd_coarse", "hash_write", "hash_accum", "adam", "input_grad", "ray_segment_sum",
+         "pose_compose", "pose_grad"]  # include/ngp_amd.h NGP_K_* order
 _UID = itertools.count(1)
 PER_ID = 8  # launches per kernel id per step (segments: one per evaluation round + 1, encode / MLP: one per round, +1 in occupancy updates)
 

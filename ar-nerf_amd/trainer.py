@@ -14,6 +14,14 @@ and every `update_interval` steps the occupancy update
 
 Per-sample buffers are allocated once at capacity n_rays * max_samples; the
 kernels read the live sample count from device memory.
+
+optimize_ext (train.py:92-95, 132-137, 148-149; off by default): the poses are
+composed with the per-image dR / dT on the device before the batch is drawn
+(pose_compose), and after the MLP backward the field's input gradients, their
+per-ray sums, the per-image chain rule (pose_grad) and a second Adam step the
+corrections -- step N's rays use ext_N, step N + 1's ext_{N+1}, so no batch is
+marched ahead of the pose Adam and its steps run eagerly: use_graphs has no
+effect under it (_pose_state, _pose_backward, _step).
 """
 from __future__ import annotations
 
@@ -48,7 +56,8 @@ class NGPTrainer:
                  update_interval=16, warmup_steps=256, max_samples=MAX_SAMPLES, sample_capacity=None, seed=4,
                  device="cuda", process_group=None, hash_backward="hybrid", bin_samples_per_ray=None, bin_level_lo=None,
                  chunk_first=64, erode=False, lambda_distortion=0.0, bin_merge_hi=None, fused_adam=True, use_graphs=True,
-                 pair_steps=False, emulate_dp=False, dp_fine_buckets=2, use_raw_HDR=False):
+                 pair_steps=False, emulate_dp=False, dp_fine_buckets=2, use_raw_HDR=False, optimize_ext=False,
+                 pose_lr=1e-6):
         self.dev = torch.device(device)
         # raw-HDR model (train.py:76-77: NGP(rgb_act='None', use_raw_HDR=True) under --use_EXR): no
         # colour activation but leaky_relu in training, relu for output_radiance
@@ -82,6 +91,15 @@ class NGPTrainer:
         # (bench --emulate-dp N; only shard 0 of each bucket is stepped, so N > 1 is for timing)
         self.dp = self.world > 1 or bool(emulate_dp)
         self.dp_world = self.world if self.world > 1 else max(1, int(emulate_dp))
+        # camera pose refinement inside the step (train.py:92-95, 132-137, 148-149; _pose_state)
+        self.optimize_ext = bool(optimize_ext)
+        self.pose_lr = float(pose_lr)  # constant: the reference's cosine schedule is the net optimizer's alone
+        self.pose_refiner = None
+        self._ps = None
+        if self.optimize_ext and self.dp:
+            raise NotImplementedError("NGPTrainer(optimize_ext=True) runs the single-process step only: the pose "
+                                      "gradient is not reduced across ranks (no process group of more than one "
+                                      "rank, no emulate_dp)")
         dev = self.dev
         # ---- field parameters: fp32 master, fp16 shadow, Adam state, grad
         self.grid = HG.HashGrid(scale)
@@ -177,7 +195,8 @@ class NGPTrainer:
         self.n_prefetched = 0
         self.no_prefetch = False  # (diagnostics) march every batch inline
         # pair_steps: two consecutive steady-state steps per graph replay (_replay_pair)
-        self.pair_steps = bool(pair_steps)
+        # (not under optimize_ext: the second step's rays depend on the first step's pose update)
+        self.pair_steps = bool(pair_steps) and not self.optimize_ext
         self._ran_ahead = False
         self._pair_key = None
         self._bind(self.msets[0])
@@ -238,7 +257,8 @@ class NGPTrainer:
         # round 1's coarse levels 0-7 encoded ahead (the next batch's first chunks, once the MLP + coarse
         # levels' Adam of this step has run, beside the binned levels' accumulation): round 1 then gathers
         # only levels 8-15 (pre_coarse = False, tests: off)
-        self.pre_coarse = True
+        # (nor under optimize_ext, where no batch is marched before the pose Adam: pre_ready stays false)
+        self.pre_coarse = not self.optimize_ext
         self.pre_levels = 8  # (the kernel's PRE_LEVELS: levels 0-7, final once the side stream's Adam has run)
         assert self.march_at in ("start", "r1", "fwd", "mlp")
         self.eval_total = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -340,6 +360,84 @@ class NGPTrainer:
     def _bind(self, m):
         for k, v in m.items():
             setattr(self, k, v)
+
+    # ------------------------------------------------------- pose refinement
+    def _pose_state(self, poses):
+        """optimize_ext: the trainer's PoseRefiner and its device state, created
+        on the first step from poses.shape[0]: fp32 Adam moments and the fp16
+        shadow the Adam launch writes (unused), the optimizer's own device step
+        count, the dense gradient, poses_eff
+        (n_img,3,4) = the poses the rays are formed from, the constant learning
+        rate, and the per-sample / per-ray gradient buffers of the chain."""
+        n = int(poses.shape[0])
+        assert poses.dtype == torch.float32 and poses.is_contiguous() and tuple(poses.shape[1:]) == (3, 4)
+        ps = self._ps
+        if ps is not None and ps["n_img"] != n:
+            raise RuntimeError(f"optimize_ext: {n} poses, the trainer refines {ps['n_img']}")
+        if ps is None:
+            from pose_refine import PoseRefiner
+            dev, R = self.dev, self.batch_size
+            f = dict(device=dev, dtype=torch.float32)
+            self.pose_refiner = PoseRefiner(n, device=dev)
+            ext = self.pose_refiner.ext.data
+            ps = self._ps = dict(
+                n_img=n, ext=ext, m=torch.zeros_like(ext), v=torch.zeros_like(ext), ext16=torch.zeros_like(ext).half(),
+                grad=torch.zeros_like(ext), poses_eff=torch.empty(n, 3, 4, **f),
+                lr=torch.full((1,), self.pose_lr, **f),
+                # the pose optimizer's own step count (its bias correction starts at 1 when the refiner is
+                # created, as the reference's second FusedAdam, whatever the trainer's step count is then)
+                step=torch.zeros(1, dtype=torch.int64, device=dev),
+                # only the gradient-carrying samples are written and read (rays_act: rays_a with each row's
+                # count cut to its n_active), so the per-sample buffers are never zeroed
+                dxyz=torch.empty(self.cap, 3, **f), ddir=torch.empty(self.cap, 3, **f),
+                rays_act=torch.zeros(R, 3, dtype=torch.int64, device=dev),
+                d_rays_o=torch.zeros(R, 3, **f), d_rays_d=torch.zeros(R, 3, **f))
+        return ps
+
+    def _pose_compose(self, poses):
+        """poses_eff = [Rod(dR) R | t + dT] on the current stream (train.py:92-95); `poses` is not modified"""
+        ps = self._pose_state(poses)
+        vren._ok(self.L.ngp_pose_compose(_p(poses), _p(ps["ext"]), ps["n_img"], _p(ps["poses_eff"]), vren._stream()),
+                 "pose_compose")
+        return ps["poses_eff"]
+
+    def _pose_backward(self, directions, poses, apply_adam):
+        """After the MLP backward, on the current stream and before any Adam of
+        this step touches params16 (the input gradients gather the hash table
+        and read the MLP weights): field input gradients over the step's own
+        list -> per-ray sums over each row's gradient-carrying samples -> the
+        chain rule to ext's dense gradient -> FusedAdam on ext (apex defaults
+        as PoseRefiner.optimizer: betas (0.9, 0.999), eps 1e-8; dense, so an
+        image absent from the batch still moves by its momentum).  The step's
+        dL/dsigma, dL/drgb carry no loss scale beyond the parameter Adam's 1 /
+        world, and the world is 1 here."""
+        ps, L, HGL, s, R = self._ps, self.L, HG._lib(), vren._stream(), self.batch_size
+        self._ev("pose_bwd", 0)
+        vren._ok(HGL.ngp_field_input_grad_pm(
+            _p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
+            HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), _p(self.enc),
+            self.cap, _p(self.drgb), _p(self.denc), self.rgb_act, _p(ps["dxyz"]), _p(ps["ddir"]), s), "field_input_grad")
+        ra = ps["rays_act"]
+        ra.copy_(self.rays_a)
+        ra[:, 2].copy_(self.n_active)
+        vren._ok(L.ngp_ray_segment_sum(_p(ps["dxyz"]), _p(ps["ddir"]), _p(self.ts), self.cap, _p(ra), R,
+                                       _p(ps["d_rays_o"]), _p(ps["d_rays_d"]), s), "ray_segment_sum")
+        vren._ok(L.ngp_pose_grad(_p(ps["d_rays_o"]), _p(ps["d_rays_d"]), _p(self.img_idxs), _p(self.pix_idxs), R,
+                                 _p(directions), _p(poses), _p(ps["ext"]), ps["n_img"], _p(ps["grad"]), s), "pose_grad")
+        if apply_adam:
+            vren._ok(L.ngp_adam_step_dev(_p(ps["ext"]), _p(ps["grad"]), _p(ps["m"]), _p(ps["v"]), _p(ps["ext16"]),
+                                         ps["ext"].numel(), _p(ps["lr"]), ctypes_float(0.9), ctypes_float(0.999),
+                                         ctypes_float(1e-8), _p(ps["step"]), ctypes_float(1.0), 0, s), "pose_adam")
+            vren._ok(L.ngp_counters_inc(_p(ps["step"]), 1, s), "pose_counter")
+        self._ev("pose_bwd", 1)
+
+    @torch.no_grad()
+    def refined_poses(self, poses):
+        """(n_img,3,4): every image's pose with its current correction applied
+        (the poses as given while optimize_ext is off or no step has run)"""
+        if self.pose_refiner is None:
+            return poses.clone()
+        return self.pose_refiner.refined_poses(poses)
 
     # ------------------------------------------------------------ schedule
     def lr(self):
@@ -511,6 +609,9 @@ class NGPTrainer:
             else:
                 _, img_idxs, pix_idxs, noise = src
                 assert img_idxs.shape[0] == R
+                if self.optimize_ext:  # (the pose gradient reads the batch's indices from the set)
+                    m["img_idxs"].copy_(img_idxs)
+                    m["pix_idxs"].copy_(pix_idxs)
                 vren._ok(L.ngp_raygen_aabb(_p(directions), _p(poses), _p(img_idxs), _p(pix_idxs), R, _p(self.center),
                                            _p(self.half_size), ctypes_float(NEAR_DISTANCE), _p(m["rays_o"]),
                                            _p(m["rays_d"]), _p(m["hits_t"]), s), "raygen")
@@ -562,7 +663,7 @@ class NGPTrainer:
         """The next batch may be marched ahead unless the next step begins with
         an occupancy update (that batch must see the new bitfield)."""
         return (self._pending is None and (self.global_step + 1) % self.update_interval != 0
-                and not self.no_prefetch)
+                and not self.no_prefetch and not self.optimize_ext)
 
     def prefetch(self, src, directions, poses):
         """March the NEXT batch into the idle buffer set on the side stream so
@@ -670,6 +771,8 @@ class NGPTrainer:
             self._ran_ahead = False
             self.global_step += 1
             return self.out_loss
+        # (optimize_ext steps are eager: nothing is marched ahead of a pose Adam, so _pending stays None
+        # and use_graphs has no effect under it)
         if (self.use_graphs and self._pending is not None and (gs % ui != 0 or self._updated_for == gs)
                 and gs >= self.warmup_steps and self.kernel_events is None and not self.no_prefetch):
             if (allow_pair and self.pair_steps and not self.dp and self.timer is None and (gs + 1) % ui != 0
@@ -992,13 +1095,18 @@ class NGPTrainer:
             if ev is not None:
                 torch.cuda.current_stream().wait_event(ev)
         else:
-            self._march(self.cur, src, directions, poses, torch.cuda.current_stream())
+            # optimize_ext: the rays of step N are those of ext_N (train.py:92-95), composed on the device
+            mp = self._pose_compose(poses) if self.optimize_ext else poses
+            self._march(self.cur, src, directions, mp, torch.cuda.current_stream())
+        if self.optimize_ext:
+            self._pose_state(poses)
+            self._pose_args = (directions, poses)
         self._bind(self.msets[self.cur])
         if rgb_gt is None:
             rgb_gt = self.rgb_gt
         self._ev("raygen_march", 1)
         fork = None
-        if next_src is not None and apply_adam:
+        if next_src is not None and apply_adam and not self.optimize_ext:
             fork = lambda: self.prefetch(next_src, directions, poses)  # noqa: E731
         if apply_adam:
             self._set_lr()
@@ -1129,6 +1237,8 @@ class NGPTrainer:
         self._ev("mlp_bwd", 1)
         if seg_done is not None:
             planned = plan(seg_done)
+        if self.optimize_ext:
+            self._pose_backward(*self._pose_args, apply_adam)
         if fork is not None and at == "mlp":
             marched = bool(fork())
         if self._segmented and hybrid:

@@ -78,6 +78,9 @@ def _declare(L):
         "ngp_active_samples": [vp, vp, c_int64, vp, vp, vp, vp],
         "ngp_gradient_rows": [vp, vp, c_int64, vp, vp, vp],
         "ngp_ray_segment_sum": [vp, vp, vp, c_int64, vp, c_int64, vp, vp, vp],
+        "ngp_pose_compose": [vp, vp, c_int64, vp, vp],
+        "ngp_pose_rod_coefficients": [vp, c_int64, vp, vp],
+        "ngp_pose_grad": [vp, vp, vp, vp, c_int64, vp, vp, vp, c_int64, vp, vp],
         "ngp_nerf_loss_fw": [vp, vp, vp, vp, c_int64, c_int, c_float, c_float, c_float, vp, vp, vp, vp],
         "ngp_nerf_loss_bw": [vp, vp, vp, vp, c_int64, c_int, c_float, c_float, c_float, vp, vp, vp, vp, vp, vp, vp],
         "ngp_chunk_counts": [vp, c_int64, c_int, vp, vp, c_float, vp, vp],

@@ -51,7 +51,7 @@ enum {
     NGP_K_SAMPLE_BATCH = 0, NGP_K_SUMMARY, NGP_K_MARCH, NGP_K_SCAN_RAYS, NGP_K_COMPACT, NGP_K_SEGMENTS,
     NGP_K_HASH_ENCODE, NGP_K_FIELD_MLP, NGP_K_CHUNK, NGP_K_COMPOSITE, NGP_K_HASH_COUNT, NGP_K_HASH_SCAN,
     NGP_K_HASH_PLAN, NGP_K_MLP_BWD, NGP_K_HASH_BWD_COARSE, NGP_K_HASH_WRITE, NGP_K_HASH_ACCUM, NGP_K_ADAM,
-    NGP_K_INPUT_GRAD, NGP_K_RAY_SEGSUM,
+    NGP_K_INPUT_GRAD, NGP_K_RAY_SEGSUM, NGP_K_POSE_COMPOSE, NGP_K_POSE_GRAD,
     NGP_K_COUNT
 };
 int ngp_timing_set(uint64_t* stamps, const int64_t* step_dev, int64_t ring, int n_ids, int per_id, uint64_t begin_mask,
@@ -384,6 +384,15 @@ int ngp_field_input_grad(const float* xyzs, const float* dirs, int64_t n, const 
                          const void* mlp_f16, const void* enc_f16, const float* dL_drgbs, const float* denc,
                          int rgb_act, float* dL_dxyzs, float* dL_ddirs, void* stream);
 
+/* ngp_field_input_grad on the training step's saved encoding: enc_f16 pair-major
+ * with row stride enc_pm_stride > 0 (the layout and stride
+ * ngp_field_backward_mlp_act takes; NGP_EINVAL otherwise: (n_samples,32) rows
+ * are ngp_field_input_grad's). */
+int ngp_field_input_grad_pm(const float* xyzs, const float* dirs, int64_t n, const int64_t* n_dev,
+                            const int32_t* sample_idx, const ngp_hashgrid_t* grid, const void* table_f16,
+                            const void* mlp_f16, const void* enc_f16, int64_t enc_pm_stride, const float* dL_drgbs,
+                            const float* denc, int rgb_act, float* dL_dxyzs, float* dL_ddirs, void* stream);
+
 /* RayMarcher.backward's two segment_csr sums (custom_functions.py:107-110): per
  * row r of rays_a (n_rays,3) i64 = (ray, start, N), over samples [start, start+N):
  *   dL_drays_o[ray] = sum dL_dxyzs;  dL_drays_d[ray] = sum (ts * dL_dxyzs + dL_ddirs)
@@ -394,6 +403,32 @@ int ngp_field_input_grad(const float* xyzs, const float* dirs, int64_t n, const 
 int ngp_ray_segment_sum(const float* dL_dxyzs, const float* dL_ddirs, const float* ts, int64_t n_samples,
                         const int64_t* rays_a, int64_t n_rays, float* dL_drays_o, float* dL_drays_d,
                         void* stream);
+
+/* Pose refinement of the fused training step (--optimize_ext, train.py:92-95,
+ * 132-137).  ext = [dR (n_img,3) | dT (n_img,3) | pad] f32, padded to a multiple
+ * of 4 floats (pose_refine.PoseRefiner's flat parameter).
+ * ngp_pose_compose: poses_out[i] = [Rod(dR_i) R_i | t_i + dT_i] for poses
+ * (n_img,3,4) f32 c2w; Rod = I + A K + B K^2 at theta = |v| + 1e-7
+ * (datasets/ray_utils.py:39-53), B without the 1 - cos cancellation.  One lane
+ * per image; dR_i = 0 returns R_i unchanged.  poses_out may not alias poses. */
+int ngp_pose_compose(const float* poses, const float* ext, int64_t n_img, float* poses_out, void* stream);
+/* The coefficients ngp_pose_compose / ngp_pose_grad evaluate, on their own (tests):
+ * out (n,4) f32 = A = sin(t)/t, B = (1 - cos t)/t^2, A' = dA/dt, B' = dB/dt at
+ * t = theta[j] > 0 (n) f32, as given (no 1e-7 guard added). */
+int ngp_pose_rod_coefficients(const float* theta, int64_t n, float* out, void* stream);
+/* The chain rule from the per-ray gradients (ngp_ray_segment_sum's outputs,
+ * (n_rays,3) f32 each) of the batch (img_idx, pix_idx (n_rays) i64, pix_idx
+ * rows of directions (HW,3) f32 -- not range-checked, as in ngp_raygen_aabb) to
+ * grad_ext, the dense gradient in ext's layout: dL/dT_i = sum dL_drays_o over
+ * the image's rays, dL/ddR_i through get_rays' transpose, R_i^T and the
+ * closed-form derivative of Rod (series for its theta-derivatives at small
+ * theta).  poses: the ORIGINAL poses, ext: the correction the rays were formed
+ * with.  Every float of grad_ext is written (zeros for images without a ray and
+ * for the padding): the caller zeroes nothing.  One block per image, fixed
+ * summation order: bit-identical from run to run. */
+int ngp_pose_grad(const float* dL_drays_o, const float* dL_drays_d, const int64_t* img_idx, const int64_t* pix_idx,
+                  int64_t n_rays, const float* directions, const float* poses, const float* ext, int64_t n_img,
+                  float* grad_ext, void* stream);
 
 /* Backward of ngp_field_forward (tcnn's backward for the three modules +
  * TruncExp.backward, custom_functions.py:169-173).  enc_f16 is the forward's

@@ -8,6 +8,9 @@ does.  The cameras are perturbed (--perturb-deg / --perturb-t) so that there is
 something to refine; the refined poses are written with --out.  Usage:
   python scripts/refine_poses.py --steps 200 --out refined_poses.pt
   python scripts/refine_poses.py --compare 30      # ms/step with / without refinement, alternated
+  python scripts/refine_poses.py --fused 30        # the same scene through NGPTrainer(optimize_ext=True):
+                                                   # ms/step of this loop and of the fused step with and without
+                                                   # refinement (alternated, all warmed), pose error before / after
 Prints one JSON line."""
 import argparse
 import json
@@ -84,6 +87,82 @@ def pose_error(a, b):
     return float(torch.rad2deg(torch.acos(cos)).mean()), float((a[:, :, 3] - b[:, :, 3]).norm(dim=1).mean())
 
 
+def fused_compare(a, tr, loop, gt, dirs, poses, true_poses):
+    """--fused: two more trainers from tr's state (parameters, Adam moments, occupancy grid, step counters), one
+    refining the poses inside the step; rounds of [drop-in loop with refinement, fused + refinement, fused] on
+    one device, each step timed between synchronisations, then 64-step windows back to back; the pose kernels'
+    times inside the step; a fresh refining trainer's pose error over --steps steps."""
+    from ktimer import KernelTimer
+    from trainer import NGPTrainer
+
+    def clone(**kw):
+        t = NGPTrainer(scale=tr.scale, batch_size=a.batch, device=tr.dev, **kw)
+        t.load_params(tr.params, tr.params16)
+        t.exp_avg.copy_(tr.exp_avg)
+        t.exp_avg_sq.copy_(tr.exp_avg_sq)
+        t.density_grid.copy_(tr.density_grid)
+        t.density_bitfield.copy_(tr.density_bitfield)
+        t.dctr.copy_(tr.dctr)
+        t.global_step = tr.global_step
+        return t
+
+    fused, plain = clone(optimize_ext=True, pose_lr=a.pose_lr), clone()
+    for _ in range(40):  # warm: the plain trainer's graph variants (with and without the occupancy update) captured
+        loop.step(True)
+        fused.train_step(gt, dirs, poses)
+        plain.train_step(gt, dirs, poses, allow_pair=False)
+    ms = {"dropin_refine": [], "fused_refine": [], "fused_plain": []}
+    runs = {"dropin_refine": lambda: loop.step(True), "fused_refine": lambda: fused.train_step(gt, dirs, poses),
+            "fused_plain": lambda: plain.train_step(gt, dirs, poses, allow_pair=False)}
+    for _ in range(a.fused):
+        for k, fn in runs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3)
+    res = {f"ms_per_step_{k}": round(statistics.median(v), 3) for k, v in ms.items()}
+    res["rounds"] = a.fused
+    res["dropin_over_fused_refine"] = round(res["ms_per_step_dropin_refine"] / res["ms_per_step_fused_refine"], 2)
+    # training throughput: windows of 64 steps back to back (4 occupancy updates each), one synchronisation per
+    # window, the three paths alternated
+    bb = {k: [] for k in runs}
+    for _ in range(5):
+        for k, fn in runs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(64):
+                fn()
+            torch.cuda.synchronize()
+            bb[k].append((time.perf_counter() - t0) * 1e3 / 64)
+    for k, v in bb.items():
+        res[f"ms_per_step_back_to_back_{k}"] = round(statistics.median(v), 3)
+    res["back_to_back_dropin_over_fused_refine"] = round(
+        res["ms_per_step_back_to_back_dropin_refine"] / res["ms_per_step_back_to_back_fused_refine"], 2)
+    # the pose kernels inside the (eager) refining step: stamp kernels around their launches
+    names = ["input_grad", "ray_segment_sum", "pose_compose", "pose_grad"]
+    timer = KernelTimer(fused.dctr, rows=64, names=names, device=tr.dev)
+    timer.arm()
+    for _ in range(32):
+        fused.train_step(gt, dirs, poses)
+    torch.cuda.synchronize()
+    timer.disarm()
+    for k, v in timer.read().items():
+        res[f"{k}_us"] = round(statistics.median(v) * 1e3, 2)
+    # convergence from the perturbed cameras: a fresh refining trainer, exactly --steps steps
+    conv = clone(optimize_ext=True, pose_lr=a.pose_lr)
+    e0 = pose_error(poses, true_poses)
+    for _ in range(a.steps):
+        conv.train_step(gt, dirs, poses)
+    torch.cuda.synchronize()
+    e1 = pose_error(conv.refined_poses(poses), true_poses)
+    res.update(steps=a.steps, rot_err_deg=[round(e0[0], 5), round(e1[0], 5)],
+               trans_err=[round(e0[1], 6), round(e1[1], 6)],
+               dR_abs_max=float(conv.pose_refiner.dR.detach().abs().max()),
+               dT_abs_max=float(conv.pose_refiner.dT.detach().abs().max()))
+    return res
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--res", type=int, default=100)
@@ -97,6 +176,11 @@ def main(argv=None):
     ap.add_argument("--compare", type=int, default=0, metavar="N",
                     help="instead: N warmed step pairs, with and without refinement alternated -> median ms/step each")
     ap.add_argument("--ktimer", action="store_true", help="with --compare: the two new kernels' time per launch")
+    ap.add_argument("--fused", type=int, default=0, metavar="N",
+                    help="instead: the perturbed scene through NGPTrainer(optimize_ext=True); N alternated rounds of "
+                         "the drop-in loop with refinement, the fused step with it and the fused step without -> "
+                         "median ms/step each, the pose kernels' time inside the step, and the pose error before "
+                         "and after --steps fused steps")
     ap.add_argument("--out", default=None, help="write {'poses', 'dR', 'dT'} here (torch.save)")
     a = ap.parse_args(argv)
     import synthetic as S
@@ -119,7 +203,9 @@ def main(argv=None):
     loop = RefineLoop(tr, gt, dirs, poses.contiguous(), a.batch, pose_lr=a.pose_lr)
     out = {"scene": f"analytic {a.res}x{a.res}x{a.images}", "batch": a.batch, "pretrain": a.pretrain,
            "pose_lr": a.pose_lr}
-    if a.compare:
+    if a.fused:
+        out.update(fused_compare(a, tr, loop, gt, dirs, poses.contiguous(), true_poses))
+    elif a.compare:
         for _ in range(5):
             loop.step(True)
             loop.step(False)

@@ -38,6 +38,12 @@ def main(argv=None):
                     help="raw-HDR model (train.py:76-77 under --use_EXR): no colour activation, leaky_relu in "
                          "training, evaluated with output_radiance=True and without the [0,1] clamp; needs fp32 "
                          "ground truth")
+    ap.add_argument("--optimize_ext", action="store_true",
+                    help="refine the training cameras inside the fused step (opt.py:54; NGPTrainer(optimize_ext=True))")
+    ap.add_argument("--pose_lr", type=float, default=1e-6, help="the reference hard-codes 1e-6 (train.py:149)")
+    ap.add_argument("--ckpt", default=None,
+                    help="write {'params'} here after training (torch.save); with --optimize_ext also 'dR' and 'dT', "
+                         "the reference checkpoint's keys for the two pose parameters")
     ap.add_argument("--sync-every", type=int, default=0, help="(diagnostics) synchronize + report every N steps")
     a = ap.parse_args(argv)
     from datasets import dataset_dict
@@ -54,7 +60,8 @@ def main(argv=None):
     # erode for COLMAP scenes, as train.py:176-178 passes erode=dataset_name=='colmap'
     mode = dict(chunk_first=0, hash_backward="atomic") if a.exact else {}
     tr = NGPTrainer(scale=a.scale, batch_size=a.batch, device=dev, num_epochs=max(1, a.steps // 1000),
-                    erode=a.dataset == "colmap", seed=a.seed, use_raw_HDR=a.use_raw_HDR, **mode)
+                    erode=a.dataset == "colmap", seed=a.seed, use_raw_HDR=a.use_raw_HDR,
+                    optimize_ext=a.optimize_ext, pose_lr=a.pose_lr, **mode)
     tr.mark_invisible_cells(train.K.to(dev), poses, train.img_wh)  # train.py:169-172
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -78,9 +85,14 @@ def main(argv=None):
         pred = out["rgb"] if a.use_raw_HDR else out["rgb"].clamp(0, 1)  # (radiance is not clamped to [0,1])
         mse = torch.mean((pred - test.rays[i].to(dev)[..., :3].float()) ** 2).item()
         psnrs.append(-10 * math.log10(max(mse, 1e-12)))
+    if a.ckpt:
+        ck = {"params": tr.full_params().detach().cpu()}
+        if tr.pose_refiner is not None:
+            ck.update({k: v.cpu() for k, v in tr.pose_refiner.state_dict_reference().items()})
+        torch.save(ck, a.ckpt)
     import vren
     res = {"dataset": a.dataset, "root": a.root, "steps": a.steps, "mode": "exact" if a.exact else "default",
-           "use_raw_HDR": bool(a.use_raw_HDR),
+           "use_raw_HDR": bool(a.use_raw_HDR), "optimize_ext": bool(a.optimize_ext),
            "guard_hits": int(vren.lib().ngp_guard_hits()),
            "train_rays_per_s": round(a.steps * a.batch / t_train, 1),
            "test_psnr": round(sum(psnrs) / max(1, len(psnrs)), 3), "test_views": n}
