@@ -218,7 +218,11 @@ __device__ __forceinline__ float start_t(const float* hits_t, const float* noise
 // moves a multiple of the binade's ulp u by the SAME multiple of u every time
 // (dt/u has no exact .5 fraction; with one, the increment is constant from
 // the second step on), so t_k = t_s + (k - s) * inc_s exactly (fmaf of an
-// exact product).  The walk (march_step) from point k goes to k + 1 when the
+// exact product).  This holds per binade only: a start at t_0 == 0 (any
+// hits_t the C ABI is handed; the product's callers clamp to NEAR_DISTANCE)
+// lies in none, and fl(k dt) from 0 parts from the serial sums within a dozen
+// points, so lat_build gives 0 a single-point segment and the closed form
+// starts at t_1 = dt.  The walk (march_step) from point k goes to k + 1 when the
 // cell at t_k is occupied, else to the first j > k with t_j >= t_target(k).
 // So one wave takes one ray: lane i evaluates lattice point c + i of a
 // 64-point window (occupancy + jump target, in parallel), then the wave
@@ -258,8 +262,11 @@ __device__ __forceinline__ int lat_build(float t0, float t2, float dt, LatSeg& s
         int n_max;  // last index offset of this segment
         float inc;
         if (!(a > ts)) return -1;  // dt below half an ulp: no progress, leave it to the serial walk
-        if (!(b < upper) || (b - a) != (a - ts)) {
-            n_max = 0;  // single-point segment (binade end or a tie step)
+        if (!(ts > 0) || !(b < upper) || (b - a) != (a - ts)) {
+            // single-point segment: binade end, a tie step, or ts == 0, which lies in no binade (frexpf gives
+            // e = 0: [0, 1) would be walked as fl(k dt), while the serial walk rounds every sum); the next
+            // point, fl(0 + dt), is in one
+            n_max = 0;
             inc = a - ts;
         } else {
             inc = a - ts;
