@@ -865,13 +865,16 @@ __device__ __forceinline__ float max4(f4 v) { return fmaxf(fmaxf(fabsf(v[0]), fa
 // is in units of the previous E; after W^T the next E is the previous one minus
 // the block's bound exponent of W^T (colsum_exp: the output stays below 2^14, no
 // per-sample max), and one power-of-two factor 2^(E_new - E_prev) re-scales it
-// (exact).
+// (exact).  A sample whose chain input is all zero (a row past the count, a
+// sample without gradient) takes E_MAX: its tiles are zeros at any scale, and it
+// must not enter the block minimum of the weight-gradient re-scale below with an
+// exponent of its own -- frexpf(0)'s exponent 0 gave it the absolute E = 14,
+// which in every block with such a row replaced "the block's largest gradient
+// at [2^13, 2^14)" and flushed the weight gradients of small upstream gradients.
 constexpr int E_MIN = -100, E_MAX = 100;
-__device__ __forceinline__ int fexp(float m) {  // m = f 2^e, f in [0.5, 1) (0 -> 0)
-    int e;
-    frexpf(m, &e);
-    return e;
-}
+// m = f 2^e, f in [0.5, 1), m >= 0: frexpf's exponent read from the biased field, so that 0 (and the
+// subnormals, which E_MAX clamps either way) gives -126: next_exp(0) = E_MAX
+__device__ __forceinline__ int fexp(float m) { return (int)(__float_as_uint(m) >> 23) - 126; }
 __device__ __forceinline__ int next_exp(float m_scaled, int e_prev) {
     return min(max(e_prev + 14 - fexp(m_scaled), E_MIN), E_MAX);
 }
@@ -1260,7 +1263,8 @@ __global__ void __launch_bounds__(64 * CW, CW / 4) field_bwd_mlp_coop_kernel(
         // (gradient) tiles of a layer are re-scaled from their per-sample exponent E_s
         // to the block's common one B = min_s E_s (the block's largest gradient at
         // [2^13, 2^14); factors <= 1, exact down to fp16 subnormals), the H tiles are
-        // the fp16 activations / encoding as they are.
+        // the fp16 activations / encoding as they are.  (All-zero samples sit at E_MAX
+        // and below: never under a sample that carries gradient; a block of none adds zeros.)
         const int Es[5] = {Eo, E4, E3, Eh, E1};
         int wmin[5];
 #pragma unroll
