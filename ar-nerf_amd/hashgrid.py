@@ -14,87 +14,21 @@ from __future__ import annotations
 
 import ctypes
 import math
-from ctypes import c_float, c_int, c_int64, c_uint32, c_void_p
+from ctypes import c_float, c_void_p
 
 import numpy as np
 import torch
 
 import vren
+from capi import C, ngp_hashgrid_t
 
-N_LEVELS = 16
-# colour-output modes of the field kernels (include/ngp_amd.h NGP_RGB_*)
-RGB_SIGMOID, RGB_NONE, RGB_LEAKY_RELU, RGB_RELU = 0, 1, 2, 3
-MLP_PARAMS = 10240
+N_LEVELS = C["NGP_MAX_LEVELS"]
+# colour-output modes of the field kernels
+RGB_SIGMOID, RGB_NONE, RGB_LEAKY_RELU, RGB_RELU = (C["NGP_RGB_" + m] for m in ("SIGMOID", "NONE", "LEAKY_RELU", "RELU"))
+MLP_PARAMS = C["NGP_MLP_PARAMS"]
 OW = {"W1": (0, 64, 32), "W2": (2048, 16, 64), "W3": (3072, 64, 32), "W4": (5120, 64, 64), "W5": (9216, 16, 64)}
 
-
-class ngp_hashgrid_t(ctypes.Structure):
-    _fields_ = [("n_levels", c_int), ("scales", c_float * 16), ("res", c_uint32 * 16), ("offsets", c_uint32 * 17),
-                ("sizes", c_uint32 * 16), ("xyz_min", c_float * 3), ("xyz_max", c_float * 3)]
-
-
-_declared = False
-
-
-def _lib():
-    global _declared
-    L = vren.lib()
-    if not _declared:
-        vp = c_void_p
-        P = ctypes.POINTER(ngp_hashgrid_t)
-        L.ngp_field_forward.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, vp]
-        L.ngp_density_forward.argtypes = [vp, c_int64, vp, P, vp, vp, vp, vp, vp]
-        L.ngp_density_input_grad.argtypes = [vp, c_int64, P, vp, vp, vp, vp, vp]
-        L.ngp_field_input_grad.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, vp, vp, c_int, vp, vp, vp]
-        L.ngp_field_input_grad_pm.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, c_int64, vp, vp, c_int, vp, vp, vp]
-        L.ngp_field_backward.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ngp_field_backward_mlp.argtypes = [vp, c_int64, vp, vp, vp, c_int64, vp, vp, vp, vp, vp, vp]
-        L.ngp_hash_encode.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp]
-        L.ngp_field_forward_indexed.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, vp, vp, vp]
-        L.ngp_field_mlp_forward.argtypes = [vp, vp, c_int64, vp, vp, vp, vp, vp, vp, vp]
-        L.ngp_field_encode_mlp.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, vp, vp, vp, vp]
-        L.ngp_field_forward_first.argtypes = [vp, vp, vp, vp, vp, vp, c_int64, c_int64, c_float, P, vp, vp, vp, vp, vp,
-                                              vp, vp, vp, vp, vp]
-        L.ngp_field_forward_first_pre.argtypes = [vp, vp, vp, vp, vp, vp, c_int64, c_int64, c_float, P, vp, vp, vp,
-                                                  vp, vp, vp, vp, vp, vp, c_int, vp]
-        # colour-output modes (raw-HDR models): the base signatures with rgb_act before the stream
-        L.ngp_field_forward_act.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, c_int, vp]
-        L.ngp_field_backward_act.argtypes = [vp, vp, c_int64, vp, P, vp, vp, vp, vp, vp, vp, vp, c_int, vp]
-        L.ngp_field_backward_mlp_act.argtypes = [vp, c_int64, vp, vp, vp, c_int64, vp, vp, vp, vp, vp, c_int, vp]
-        L.ngp_field_encode_mlp_act.argtypes = [vp, vp, c_int64, vp, vp, P, vp, vp, vp, vp, vp, vp, c_int, vp]
-        L.ngp_field_forward_first_pre_act.argtypes = [vp, vp, vp, vp, vp, vp, c_int64, c_int64, c_float, P, vp, vp,
-                                                      vp, vp, vp, vp, vp, vp, vp, c_int, c_int, vp]
-        L.ngp_field_encode_first_coarse.argtypes = [vp, vp, vp, vp, c_int64, c_int64, P, vp, vp, vp]
-        L.ngp_hash_backward.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp]
-        L.ngp_hash_backward_binned.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp, c_int64, c_int, c_int, vp]
-        L.ngp_hash_backward_levels.argtypes = [vp, c_int64, vp, vp, P, vp, vp, c_int, c_int, vp]
-        L.ngp_hash_backward_levels_rep.argtypes = [vp, c_int64, vp, vp, P, vp, vp, c_int, c_int, vp, c_int, c_int, c_int,
-                                                   vp]
-        L.ngp_hash_backward_rep_floats.argtypes = [P, c_int, c_int]
-        L.ngp_hash_backward_rep_floats.restype = ctypes.c_size_t
-        L.ngp_hash_binned_plan.argtypes = [vp, c_int64, vp, vp, P, vp, c_int64, c_int, c_int, vp]
-        L.ngp_hash_binned_apply.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp, c_int64, c_int, c_int, vp]
-        L.ngp_hash_binned_write.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp, c_int64, c_int, c_int, vp]
-        L.ngp_hash_binned_accum.argtypes = [P, vp, vp, c_int64, c_int, c_int, vp]
-        L.ngp_hash_binned_accum_levels.argtypes = [P, vp, vp, c_int64, c_int, c_int, c_int, c_int, vp]
-        L.ngp_hash_binned_apply_adam.argtypes = [vp, c_int64, vp, vp, P, vp, vp, vp, c_int64, c_int, c_int, vp, vp, vp,
-                                                 vp, vp, c_float, c_float, c_float, vp, c_float, vp]
-        L.ngp_hash_binned_accum_adam.argtypes = [P, vp, vp, c_int64, c_int, c_int, vp, vp, vp, vp, vp, c_float, c_float,
-                                                 c_float, vp, c_float, vp]
-        L.ngp_hash_backward_binned_workspace.argtypes = [c_int64]
-        L.ngp_hash_backward_binned_workspace.restype = ctypes.c_size_t
-        for f in (L.ngp_field_forward, L.ngp_density_forward, L.ngp_density_input_grad, L.ngp_field_backward, L.ngp_field_backward_mlp,
-                  L.ngp_hash_encode, L.ngp_field_mlp_forward, L.ngp_field_forward_indexed, L.ngp_field_encode_mlp,
-                  L.ngp_hash_backward, L.ngp_hash_backward_binned, L.ngp_hash_backward_levels,
-                  L.ngp_hash_backward_levels_rep,
-                  L.ngp_hash_binned_plan, L.ngp_hash_binned_apply, L.ngp_hash_binned_write,
-                  L.ngp_hash_binned_accum, L.ngp_hash_binned_accum_levels, L.ngp_hash_binned_apply_adam,
-                  L.ngp_hash_binned_accum_adam, L.ngp_field_forward_act, L.ngp_field_backward_act,
-                  L.ngp_field_backward_mlp_act, L.ngp_field_encode_mlp_act, L.ngp_field_forward_first_pre_act,
-                  L.ngp_field_input_grad, L.ngp_field_input_grad_pm):
-            f.restype = c_int
-        _declared = True
-    return L
+_lib = vren.lib  # the one loader, under the name this module's callers use
 
 
 def _ptr(t):
@@ -111,11 +45,11 @@ class HashGrid:
         self.base_resolution, self.per_level_scale = base_resolution, per_level_scale
         d = ngp_hashgrid_t()
         d.n_levels = n_levels
-        self.n_entries = int(vren.lib().ngp_hashgrid_levels(n_levels, log2_T, base_resolution, c_float(per_level_scale),
-                                                            ctypes.cast(d.scales, c_void_p),
-                                                            ctypes.cast(d.res, c_void_p),
-                                                            ctypes.cast(d.offsets, c_void_p),
-                                                            ctypes.cast(d.sizes, c_void_p)))
+        self.n_entries = int(_lib().ngp_hashgrid_levels(n_levels, log2_T, base_resolution, c_float(per_level_scale),
+                                                        ctypes.cast(d.scales, c_void_p),
+                                                        ctypes.cast(d.res, c_void_p),
+                                                        ctypes.cast(d.offsets, c_void_p),
+                                                        ctypes.cast(d.sizes, c_void_p)))
         for i in range(3):
             d.xyz_min[i] = -scale
             d.xyz_max[i] = scale
@@ -305,7 +239,7 @@ def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL
     L, s = _lib(), vren._stream()
     idx = torch.empty(n, dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int64, device=dev)
-    vren._ok(vren.lib().ngp_gradient_rows(_ptr(dL_dsig), _ptr(dL_drgb), n, _ptr(idx), _ptr(cnt), s), "gradient_rows")
+    vren._ok(L.ngp_gradient_rows(_ptr(dL_dsig), _ptr(dL_drgb), n, _ptr(idx), _ptr(cnt), s), "gradient_rows")
     denc = torch.empty(n, 32, device=dev)
     vren._ok(L.ngp_field_backward_mlp_act(_ptr(dirs), n, _ptr(cnt), _ptr(idx), _ptr(enc), 0, _ptr(params16),
                                           _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc), _ptr(mlp_grad), int(rgb_act), s),

@@ -19,6 +19,7 @@ from ctypes import c_int32
 import torch
 
 import vren
+from capi import C
 
 NAMES = ["sample_batch", "bitfield_summary", "march", "scan_rays", "march_compact", "segments", "hash_encode",
          "field_mlp", "chunk_rest", "composite_loss", "hash_count", "hash_scan", "hash_plan", "mlp_bwd",
@@ -29,7 +30,7 @@ PER_ID = 8  # launches per kernel id per step (segments: one per evaluation roun
 
 
 def _lib():
-    return vren.lib()  # signatures declared in vren._declare
+    return vren.lib()
 
 
 class KernelTimer:
@@ -126,6 +127,7 @@ class KernelTimer:
 PROBES = ["march", "first_chunk", "field_encode_mlp", "composite_loss", "mlp_bwd", "hash_bwd_coarse", "hash_count",
           "hash_write", "hash_accum", "adam", "segments", "rays_nonempty", "counters_inc", "hash_plan", "adam_residual",
           "march_compact", "sample_batch", "pre_encode"]
+assert len(NAMES) == C["NGP_K_COUNT"] and len(PROBES) == C["NGP_P_COUNT"], "name lists out of step with ngp_amd.h"
 
 
 class ProbeTimer:
@@ -139,7 +141,7 @@ class ProbeTimer:
     keeps its last `rows` steps).  Usage: arm(); run steps; disarm();
     summary(skip_rows=...)."""
 
-    WAVES = 65536  # NGP_PROBE_WAVES
+    WAVES = C["NGP_PROBE_WAVES"]
 
     def __init__(self, step_counter, rows=32, device="cuda"):
         assert _lib().ngp_probe_count() == len(PROBES)

@@ -27,10 +27,11 @@ import torch
 
 import hashgrid as HG
 import vren
+from capi import C
 
 MAX_SAMPLES = 1024     # models/rendering.py:7
 NEAR_DISTANCE = 0.01   # models/rendering.py:8
-STATE_WORDS = 8        # NGP_RENDER_STATE_WORDS
+STATE_WORDS = C["NGP_RENDER_STATE_WORDS"]
 RS_ACTIVE, RS_VALID, RS_TOTAL, RS_ITERS = 4, 5, 6, 7
 
 
@@ -64,7 +65,7 @@ class TestRenderer:
         # graph A: frame opening + K iterations; graph B (replayed while the loop runs): K_tail
         self.K, self.K_tail, self.use_graphs = int(iters_per_graph), int(iters_tail), bool(use_graphs)
         self.bg = (ctypes.c_float * 3)(*[float(b) for b in bg_rgb])
-        L = HG._lib()
+        L = vren.lib()
         self.cap = int(L.ngp_render_test_capacity(self.n_rays, self.min_samples))
         n, cap = self.n_rays, self.cap
         f = dict(device=dev, dtype=torch.float32)
@@ -95,7 +96,7 @@ class TestRenderer:
     # ------------------------------------------------------------ pieces
     def _iteration(self, k):
         """One loop iteration (rendering.py:186-236) on the current stream."""
-        L, s, par = HG._lib(), vren._stream(), k & 1
+        L, s, par = vren.lib(), vren._stream(), k & 1
         vren._ok(L.ngp_render_test_march(_p(self.rays_o), _p(self.rays_d), _p(self.hits_t), self.n_rays,
                                          _p(self.bitfield), self.cascades, self.grid_size, c_float(self.scale),
                                          c_float(self.esf), MAX_SAMPLES, self.min_samples, self.max_samples, par,
@@ -115,7 +116,7 @@ class TestRenderer:
                                              _p(self.depth), _p(self.rgb), s), "render_test_composite")
 
     def _begin(self):
-        L, s = HG._lib(), vren._stream()
+        L, s = vren.lib(), vren._stream()
         vren._ok(L.ngp_render_test_begin(self.n_rays, _p(self.state), _p(self.alive[0]), _p(self.opacity),
                                          _p(self.depth), _p(self.rgb), s), "render_test_begin")
         vren.bitfield_summary(self.bitfield, self.grid_size, out=self.summary)
@@ -155,8 +156,8 @@ class TestRenderer:
         if bg_sh is not None:
             vren.render_test_finish_sh(self.opacity, self.rays_d, bg_sh, self.rgb)
         else:
-            vren._ok(HG._lib().ngp_render_test_finish(_p(self.opacity), self.n_rays, self.bg, _p(self.rgb),
-                                                      vren._stream()), "render_test_finish")
+            vren._ok(vren.lib().ngp_render_test_finish(_p(self.opacity), self.n_rays, self.bg, _p(self.rgb),
+                                                       vren._stream()), "render_test_finish")
         return {"opacity": self.opacity, "depth": self.depth, "rgb": self.rgb,
                 "total_samples": self.state[RS_TOTAL]}
 

@@ -35,6 +35,7 @@ import torch.distributed as dist
 import ddp
 import hashgrid as HG
 import vren
+from capi import C
 
 MAX_SAMPLES = 1024  # models/rendering.py:9
 NEAR_DISTANCE = 0.01  # models/rendering.py:10
@@ -45,7 +46,7 @@ def _p(t):
     return HG._ptr(t)
 
 
-STAT_STRIPES, STAT_STRIDE = 32, 16  # include/ngp_amd.h NGP_STAT_*
+STAT_STRIPES, STAT_STRIDE = C["NGP_STAT_STRIPES"], C["NGP_STAT_STRIDE"]
 THROTTLE_EVERY, THROTTLE_DEPTH = 32, 4  # host run-ahead bound: <= 160 steps enqueued
 COARSE_REP, COARSE_REP_LEVELS = 8, 4  # gradient replicas of the coarsest atomic levels
 
@@ -282,7 +283,7 @@ class NGPTrainer:
         self.bin_merge_hi = int(bin_merge_hi)
         if hash_backward != "atomic":
             self.bin_max_samples = R * bin_samples_per_ray
-            nbytes = HG._lib().ngp_hash_backward_binned_workspace(self.bin_max_samples)
+            nbytes = vren.lib().ngp_hash_backward_binned_workspace(self.bin_max_samples)
             self.bin_ws = torch.empty((nbytes + 255) // 256, 64, dtype=torch.int32, device=dev)
         # coarse atomic levels [0, coarse_rep_levels) add into coarse_rep replicas of their
         # gradient range, folded afterwards (ngp_hash_backward_levels_rep): the coarsest
@@ -293,8 +294,8 @@ class NGPTrainer:
         self.coarse_rep_levels = min(COARSE_REP_LEVELS, self.bin_level_lo) if hash_backward != "atomic" else 0
         self.rep_buf = None
         if self.coarse_rep > 0 and self.coarse_rep_levels > 0:
-            nrep = HG._lib().ngp_hash_backward_rep_floats(HG.ctypes.byref(self.grid.desc), self.coarse_rep_levels,
-                                                          self.coarse_rep)
+            nrep = vren.lib().ngp_hash_backward_rep_floats(HG.ctypes.byref(self.grid.desc), self.coarse_rep_levels,
+                                                           self.coarse_rep)
             self.rep_buf = torch.zeros(nrep, **f)
         self.bg = torch.ones(3, **f) if self.esf == 0 else torch.zeros(3, **f)  # models/rendering.py:287-296
         self._bg_rand = torch.zeros(3, **f)
@@ -322,7 +323,6 @@ class NGPTrainer:
         self._graphs = {}
         self._graph_post = {}
         self.L = vren.lib()
-        HG._lib()
         # {"field_fwd"|"mlp_bwd"|"hash_bwd"|stage: (start, end) torch.cuda.Event} (eager diagnostics)
         self.kernel_events = None
         # ktimer.KernelTimer (bench): graph replays carry HIP events around every kernel
@@ -411,9 +411,9 @@ class NGPTrainer:
         image absent from the batch still moves by its momentum).  The step's
         dL/dsigma, dL/drgb carry no loss scale beyond the parameter Adam's 1 /
         world, and the world is 1 here."""
-        ps, L, HGL, s, R = self._ps, self.L, HG._lib(), vren._stream(), self.batch_size
+        ps, L, s, R = self._ps, self.L, vren._stream(), self.batch_size
         self._ev("pose_bwd", 0)
-        vren._ok(HGL.ngp_field_input_grad_pm(
+        vren._ok(L.ngp_field_input_grad_pm(
             _p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
             HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), _p(self.enc),
             self.cap, _p(self.drgb), _p(self.denc), self.rgb_act, _p(ps["dxyz"]), _p(ps["ddir"]), s), "field_input_grad")
@@ -554,20 +554,20 @@ class NGPTrainer:
                 n = hi - lo
                 if self.occ_keep:
                     # encode + density net of the kept samples only (sigma written at their position)
-                    vren._ok(HG._lib().ngp_field_encode_mlp(_p(self._occ_xyz), None, n, _p(self._occ_kept_n),
-                                                            _p(self._occ_kept), HG.ctypes.byref(self.grid.desc),
-                                                            _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
-                                                            None, _p(self._occ_sig), None, None, s),
+                    vren._ok(self.L.ngp_field_encode_mlp(_p(self._occ_xyz), None, n, _p(self._occ_kept_n),
+                                                         _p(self._occ_kept), HG.ctypes.byref(self.grid.desc),
+                                                         _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
+                                                         None, _p(self._occ_sig), None, None, s),
                              "density_encode_mlp")
                     vren._ok(L.ngp_density_scatter_kept(_p(self._occ_kept), _p(self._occ_kept_n), n,
                                                         _p(self._occ_flat), _p(self._occ_sig), 0, _p(key), s),
                              "density_scatter_kept")
                     continue
                 # encode + density net in one launch (no encoding kept)
-                vren._ok(HG._lib().ngp_field_encode_mlp(_p(self._occ_xyz), None, n, None, None,
-                                                        HG.ctypes.byref(self.grid.desc),
-                                                        _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), None,
-                                                        _p(self._occ_sig), None, None, s), "density_encode_mlp")
+                vren._ok(self.L.ngp_field_encode_mlp(_p(self._occ_xyz), None, n, None, None,
+                                                     HG.ctypes.byref(self.grid.desc),
+                                                     _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), None,
+                                                     _p(self._occ_sig), None, None, s), "density_encode_mlp")
                 sig, flat = self._occ_sig, self._occ_flat
             # density_grid_tmp[c, indices] = sigma, list positions lo + i (rank shards)
             vren._ok(L.ngp_density_scatter_last(_p(flat), _p(sig), n, lo, _p(key), s), "density_scatter_last")
@@ -977,7 +977,7 @@ class NGPTrainer:
     def _coarse_levels(self, fold=True):
         """The atomic coarse hash levels [0, bin_level_lo) on the current stream
         (fold=False: their replicated part stays in rep_buf for the accumulation)."""
-        vren._ok(HG._lib().ngp_hash_backward_levels_rep(
+        vren._ok(self.L.ngp_hash_backward_levels_rep(
             _p(self.xyzs), self.cap, _p(self.n_active_total), _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
             _p(self.denc), _p(self.grad[HG.MLP_PARAMS:]), 0, self.bin_level_lo,
             _p(self.rep_buf) if self.rep_buf is not None else None,
@@ -994,16 +994,16 @@ class NGPTrainer:
         range's bucket chain on the comm stream); segment 0 first writes the
         binned levels' records."""
         if r == 0:
-            HGL = HG._lib()
-            vren._ok(HGL.ngp_hash_binned_write(_p(self.xyzs), self.cap, _p(self.n_active_total),
-                                               _p(self.sample_idx), HG.ctypes.byref(self.grid.desc), _p(self.denc),
-                                               _p(self.grad[HG.MLP_PARAMS:]), _p(self.bin_ws), self.bin_max_samples,
-                                               self.bin_level_lo, self.bin_merge_hi, vren._stream()),
+            vren._ok(self.L.ngp_hash_binned_write(_p(self.xyzs), self.cap, _p(self.n_active_total),
+                                                  _p(self.sample_idx), HG.ctypes.byref(self.grid.desc), _p(self.denc),
+                                                  _p(self.grad[HG.MLP_PARAMS:]), _p(self.bin_ws),
+                                                  self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi,
+                                                  vren._stream()),
                      "hash_binned_write")
         self._accum_levels(self.bin_cuts[r], self.bin_cuts[r + 1])
 
     def _accum_levels(self, lo, hi):
-        vren._ok(HG._lib().ngp_hash_binned_accum_levels(
+        vren._ok(self.L.ngp_hash_binned_accum_levels(
             HG.ctypes.byref(self.grid.desc), _p(self.grad[HG.MLP_PARAMS:]), _p(self.bin_ws), self.bin_max_samples,
             self.bin_level_lo, self.bin_merge_hi, lo, hi, vren._stream()), "hash_binned_accum_levels")
 
@@ -1127,7 +1127,7 @@ class NGPTrainer:
         profiles/r04/ab/march_fork_position.txt); before the row forward, at
         the step's start (round 2: +1.5 % against after the composite,
         profiles/r02/ab/prefetch_at.txt)."""
-        L, s, HGL, R = self.L, vren._stream(), HG._lib(), self.batch_size
+        L, s, R = self.L, vren._stream(), self.batch_size
         at = self.march_fork_point()
         marched = False  # the next batch marched beside this step (fork() said so)
         if fork is not None and at == "start":
@@ -1141,7 +1141,7 @@ class NGPTrainer:
             m = self.msets[self.cur]
             pre = 8 if m["pre_ready"] else 0
             m["pre_ready"] = False
-            vren._ok(HGL.ngp_field_forward_first_pre_act(
+            vren._ok(L.ngp_field_forward_first_pre_act(
                 _p(self.xyzs), _p(self.dirs), _p(self.deltas), _p(self.rays_a), _p(self.rows_ne), _p(self.n_rows_ne),
                 R, self.cap, ctypes_float(1e-4), HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
                 _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs), None, _p(self.eval_idx),
@@ -1175,10 +1175,10 @@ class NGPTrainer:
             self._field_indexed(s)
         else:  # encode + MLPs in one launch over every marched sample
             self._ev("hash_encode", 0)
-            vren._ok(HGL.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_samples), None,
-                                                  HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
-                                                  _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs),
-                                                  None, self.rgb_act, s), "field_encode_mlp")
+            vren._ok(L.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_samples), None,
+                                                HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
+                                                _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs),
+                                                None, self.rgb_act, s), "field_encode_mlp")
             self._ev("hash_encode", 1)
         self._ev("field_fwd", 1)
         if fork is not None and at == "fwd":
@@ -1213,10 +1213,10 @@ class NGPTrainer:
             else:
                 bs.wait_event(after)
             with torch.cuda.stream(bs):
-                vren._ok(HGL.ngp_hash_binned_plan(_p(self.xyzs), self.cap, _p(self.n_active_total),
-                                                  _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
-                                                  _p(self.bin_ws), self.bin_max_samples, self.bin_level_lo,
-                                                  self.bin_merge_hi, vren._stream()), "hash_binned_plan")
+                vren._ok(L.ngp_hash_binned_plan(_p(self.xyzs), self.cap, _p(self.n_active_total),
+                                                _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
+                                                _p(self.bin_ws), self.bin_max_samples, self.bin_level_lo,
+                                                self.bin_merge_hi, vren._stream()), "hash_binned_plan")
                 ev = torch.cuda.Event()
                 ev.record(bs)
             return ev
@@ -1230,10 +1230,10 @@ class NGPTrainer:
             seg_done = torch.cuda.Event()
             seg_done.record(cs)
         self._ev("mlp_bwd", 0)
-        vren._ok(HGL.ngp_field_backward_mlp_act(_p(self.dirs), self.cap, _p(self.n_active_total),
-                                                _p(self.sample_idx), _p(self.enc), self.cap, _p(self.params16),
-                                                _p(self.dsig), _p(self.drgb), _p(self.denc), _p(self.grad),
-                                                self.rgb_act, s), "field_backward_mlp")
+        vren._ok(L.ngp_field_backward_mlp_act(_p(self.dirs), self.cap, _p(self.n_active_total),
+                                              _p(self.sample_idx), _p(self.enc), self.cap, _p(self.params16),
+                                              _p(self.dsig), _p(self.drgb), _p(self.denc), _p(self.grad),
+                                              self.rgb_act, s), "field_backward_mlp")
         self._ev("mlp_bwd", 1)
         if seg_done is not None:
             planned = plan(seg_done)
@@ -1285,7 +1285,7 @@ class NGPTrainer:
                         if pre:
                             # the next batch (marched beside this step) gets its round-1 coarse levels now
                             nx = self.msets[1 - self.cur]
-                            vren._ok(HGL.ngp_field_encode_first_coarse(
+                            vren._ok(L.ngp_field_encode_first_coarse(
                                 _p(nx["xyzs"]), _p(nx["rays_a"]), _p(nx["rows_ne"]), _p(nx["n_rows_ne"]), R,
                                 self.cap, HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
                                 _p(self.enc), vren._stream()), "encode_first_coarse")
@@ -1302,7 +1302,7 @@ class NGPTrainer:
             if binned:  # (none at bin_level_lo == L: the side stream took every level and its Adam)
                 cs.wait_event(planned)
                 if fused:  # + FusedAdam of the binned levels inside the accumulation
-                    vren._ok(HGL.ngp_hash_binned_apply_adam(
+                    vren._ok(L.ngp_hash_binned_apply_adam(
                         _p(self.xyzs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
                         HG.ctypes.byref(self.grid.desc), _p(self.denc), _p(self.grad[t:]), _p(self.bin_ws),
                         self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi, _p(self.params[t:]),
@@ -1310,10 +1310,10 @@ class NGPTrainer:
                         ctypes_float(0.9), ctypes_float(0.999), ctypes_float(1e-15), _p(self.dctr),
                         ctypes_float(1.0 / self.world), s), "hash_binned_apply_adam")
                 else:
-                    vren._ok(HGL.ngp_hash_binned_apply(_p(self.xyzs), self.cap, _p(self.n_active_total),
-                                                       _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
-                                                       _p(self.denc), _p(self.grad[t:]), _p(self.bin_ws),
-                                                       self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi, s),
+                    vren._ok(L.ngp_hash_binned_apply(_p(self.xyzs), self.cap, _p(self.n_active_total),
+                                                     _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
+                                                     _p(self.denc), _p(self.grad[t:]), _p(self.bin_ws),
+                                                     self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi, s),
                              "hash_binned_apply")
                     if adam_split:
                         self._adam(split, self.n_params, s)
@@ -1325,9 +1325,9 @@ class NGPTrainer:
                 self._ev("hash_bwd", 1)
                 return self.out_loss
         else:
-            vren._ok(HGL.ngp_hash_backward(_p(self.xyzs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
-                                           HG.ctypes.byref(self.grid.desc),
-                                           _p(self.denc), _p(self.grad[HG.MLP_PARAMS:]), s), "hash_backward")
+            vren._ok(L.ngp_hash_backward(_p(self.xyzs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
+                                         HG.ctypes.byref(self.grid.desc),
+                                         _p(self.denc), _p(self.grad[HG.MLP_PARAMS:]), s), "hash_backward")
         self._ev("hash_bwd", 1)
         if not self.dp and apply_adam:
             self._ev("adam", 0)
@@ -1410,11 +1410,11 @@ class NGPTrainer:
         idx = self.eval_idx if idx is None else idx
         total = self.eval_total if total is None else total
         self._ev("hash_encode", 0)
-        vren._ok(HG._lib().ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(total),
-                                                    _p(idx), HG.ctypes.byref(self.grid.desc),
-                                                    _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
-                                                    _p(self.enc), _p(self.sigmas), _p(self.rgbs), None,
-                                                    self.rgb_act, s), "field_encode_mlp")
+        vren._ok(self.L.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(total),
+                                                 _p(idx), HG.ctypes.byref(self.grid.desc),
+                                                 _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
+                                                 _p(self.enc), _p(self.sigmas), _p(self.rgbs), None,
+                                                 self.rgb_act, s), "field_encode_mlp")
         self._ev("hash_encode", 1)
 
     # ---------------------------------------------------- test-time render

@@ -22,9 +22,11 @@ import contextlib
 import ctypes
 import gc
 import os
-from ctypes import c_float, c_int, c_int64, c_void_p
+from ctypes import c_float, c_void_p  # noqa: F401  (c_float: callers wrap float arguments as vren.c_float)
 
 import torch
+
+import capi
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NGP_AMD_LIB", os.path.join(_HERE, "lib", "libngp_amd.so"))
@@ -36,119 +38,16 @@ class NGPError(RuntimeError):
     pass
 
 
-def _declare(L):
-    vp = c_void_p
-    sig = {
-        "ngp_ray_aabb_intersect": [vp, vp, c_int64, vp, vp, c_int, c_int, vp, vp, vp, vp],
-        "ngp_raygen_aabb": [vp, vp, vp, vp, c_int64, vp, vp, c_float, vp, vp, vp, vp],
-        "ngp_sample_batch": [ctypes.c_uint64, ctypes.c_uint64, c_int64, vp, c_int, c_int64, c_int64, vp, vp, c_int64,
-                             vp, vp, c_float, vp, vp, vp, vp, vp, vp, vp, vp],
-        "ngp_sample_batch_dev": [ctypes.c_uint64, vp, c_int64, c_int64, vp, c_int, c_int64, c_int64, vp, vp, c_int64,
-                                 vp, vp, c_float, vp, vp, vp, vp, vp, vp, vp, vp],
-        "ngp_adam_step_dev": [vp, vp, vp, vp, vp, c_int64, vp, c_float, c_float, c_float, vp, c_float, c_int, vp],
-        "ngp_adam_step_dev_zero": [vp, vp, vp, vp, vp, c_int64, vp, c_float, c_float, c_float, vp, c_float, c_int, vp,
-                                   c_int64, vp],
-        "ngp_adam_step_dev_rep": [vp, vp, vp, vp, vp, c_int64, vp, c_float, c_float, c_float, vp, c_float, c_int, vp,
-                                  c_int64, c_int64, c_int, vp],
-        "ngp_counters_inc": [vp, c_int, vp],
-        "ngp_random_bg": [ctypes.c_uint64, vp, c_int64, vp, vp],
-        "ngp_occupied_cells": [vp, c_int64, c_float, vp, vp, vp, vp],
-        "ngp_occupancy_samples": [ctypes.c_uint64, vp, c_int, c_int, c_int64, c_float, c_float, vp, vp, c_int64,
-                                  c_int64, vp, vp, vp],
-        "ngp_occupancy_samples_sorted": [ctypes.c_uint64, vp, c_int, c_int, c_int64, c_float, c_float, vp, vp,
-                                         c_int64, c_int64, vp, vp, vp, vp],
-        "ngp_morton3d": [vp, c_int64, vp, vp],
-        "ngp_morton3d_invert": [vp, c_int64, vp, vp],
-        "ngp_packbits": [vp, c_int64, c_float, vp, vp, vp],
-        "ngp_march_train_count": [vp, vp, vp, c_int64, vp, c_int, c_int, c_float, c_float, vp, c_int, vp, vp, vp, vp],
-        "ngp_march_train_write": [vp, vp, vp, c_int64, vp, c_int, c_int, c_float, c_float, vp, c_int, vp, vp, vp, vp,
-                                  vp, vp],
-        "ngp_march_train_slots": [vp, vp, vp, c_int64, vp, c_int, c_int, c_float, c_float, vp, c_int, vp, vp, vp, vp,
-                                  vp, vp, vp],
-        "ngp_bitfield_summary": [vp, c_int64, c_int, vp, vp],
-        "ngp_march_train_compact": [vp, vp, vp, c_int64, vp, vp, c_int, vp, vp, vp, vp, vp],
-        "ngp_march_test": [vp, vp, vp, vp, c_int64, vp, c_int, c_int, c_float, c_float, c_int, c_int, vp, vp, vp, vp,
-                           vp, vp, vp],
-        "ngp_composite_train_fw": [vp, vp, vp, vp, vp, c_int64, c_float, vp, vp, vp, vp, vp, vp],
-        "ngp_composite_train_bw": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int64, vp, vp, vp, c_float, vp, vp, vp],
-        "ngp_composite_test_fw": [vp, vp, vp, vp, c_int64, c_int, vp, c_float, vp, vp, vp, vp, vp],
-        "ngp_composite_loss": [vp, vp, vp, vp, vp, c_int64, vp, vp, c_int, c_float, c_float, c_float, c_float, c_float,
-                               vp,
-                               vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "ngp_active_samples": [vp, vp, c_int64, vp, vp, vp, vp],
-        "ngp_gradient_rows": [vp, vp, c_int64, vp, vp, vp],
-        "ngp_ray_segment_sum": [vp, vp, vp, c_int64, vp, c_int64, vp, vp, vp],
-        "ngp_pose_compose": [vp, vp, c_int64, vp, vp],
-        "ngp_pose_rod_coefficients": [vp, c_int64, vp, vp],
-        "ngp_pose_grad": [vp, vp, vp, vp, c_int64, vp, vp, vp, c_int64, vp, vp],
-        "ngp_nerf_loss_fw": [vp, vp, vp, vp, c_int64, c_int, c_float, c_float, c_float, vp, vp, vp, vp],
-        "ngp_nerf_loss_bw": [vp, vp, vp, vp, c_int64, c_int, c_float, c_float, c_float, vp, vp, vp, vp, vp, vp, vp],
-        "ngp_chunk_counts": [vp, c_int64, c_int, vp, vp, c_float, vp, vp],
-        "ngp_chunk_counts_range": [vp, c_int64, c_int, c_int, vp, vp, c_float, vp, vp],
-        "ngp_ray_segments": [vp, vp, c_int64, c_int, vp, vp, vp, vp, vp],
-        "ngp_rays_nonempty": [vp, c_int64, vp, vp, vp, vp, vp],
-        "ngp_chunk_segments": [vp, vp, vp, c_int64, c_int, c_int, c_float, vp, vp, vp, vp, vp, vp, vp],
-        "ngp_ray_segments_capped": [vp, c_int64, c_int, vp, vp, vp, vp, vp],
-        "ngp_adam_step": [vp, vp, vp, vp, vp, c_int64, c_float, c_float, c_float, c_float, c_int64, c_float, c_int,
-                          vp],
-        "ngp_density_scatter_last": [vp, vp, c_int64, c_int64, vp, vp],
-        "ngp_occupancy_keep": [vp, c_int64, c_int64, c_int64, c_int64, c_int64, vp, vp, vp, vp],
-        "ngp_density_scatter_kept": [vp, vp, c_int64, vp, vp, c_int64, vp, vp],
-        "ngp_density_grid_ema": [vp, vp, c_int64, c_float, vp, c_float, vp, vp, vp],
-        "ngp_distortion_loss_fw": [vp, vp, vp, vp, c_int64, vp, vp, vp, vp],
-        "ngp_distortion_loss_bw": [vp, vp, vp, vp, vp, vp, vp, c_int64, vp, vp],
-        "ngp_render_test_begin": [c_int64, vp, vp, vp, vp, vp, vp],
-        "ngp_render_test_march": [vp, vp, vp, c_int64, vp, c_int, c_int, c_float, c_float, c_int, c_int, c_int64,
-                                  c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "ngp_render_test_composite": [vp, vp, vp, vp, vp, c_int64, c_int, vp, vp, vp, c_float, vp, vp, vp, vp],
-        "ngp_render_test_finish": [vp, c_int64, vp, vp, vp],
-        "ngp_probe_rays": [vp, vp, c_int, c_int64, c_int64, vp, vp, c_float, vp, vp, vp, vp],
-        "ngp_render_test_finish_sh": [vp, vp, c_int64, vp, vp, vp],
-        "ngp_probe_sh9_project": [vp, vp, vp, c_int64, c_int64, vp, vp, vp],
-    }
-    for name, args in sig.items():
-        f = getattr(L, name)
-        f.argtypes = args
-        f.restype = c_int
-    L.ngp_version.restype = ctypes.c_char_p
-    L.ngp_hashgrid_levels.argtypes = [c_int, c_int, c_int, c_float, vp, vp, vp, vp]
-    L.ngp_hashgrid_levels.restype = ctypes.c_uint32
-    L.ngp_occupancy_sorted_workspace.argtypes = [c_int64]
-    L.ngp_occupancy_sorted_workspace.restype = ctypes.c_size_t
-    L.ngp_occupied_cells_workspace.argtypes = [c_int64]
-    L.ngp_occupied_cells_workspace.restype = ctypes.c_size_t
-    L.ngp_chunk_segments_workspace.argtypes = [c_int64]
-    L.ngp_chunk_segments_workspace.restype = ctypes.c_size_t
-    L.ngp_render_test_capacity.argtypes = [c_int64, c_int]
-    L.ngp_render_test_capacity.restype = c_int64
-    L.ngp_guard_hits.argtypes = []
-    L.ngp_guard_hits.restype = ctypes.c_ulonglong
-    L.ngp_guard_reset.argtypes = []
-    L.ngp_guard_reset.restype = c_int
-    # measurement hook (ktimer.py)
-    L.ngp_timing_set.argtypes = [vp, vp, c_int64, c_int, c_int, ctypes.c_uint64, ctypes.c_uint64]
-    L.ngp_timing_set.restype = c_int
-    L.ngp_timing_counts.argtypes = [vp, c_int]
-    L.ngp_timing_counts.restype = c_int
-    L.ngp_timing_tick_ns.argtypes = []
-    L.ngp_timing_tick_ns.restype = ctypes.c_double
-    L.ngp_probe_set.argtypes = [vp, vp, c_int64]
-    L.ngp_probe_set.restype = c_int
-    L.ngp_probe_count.argtypes = []
-    L.ngp_probe_count.restype = c_int
-    L.ngp_trace_marker.argtypes = [c_int, vp]
-    L.ngp_trace_marker.restype = c_int
-
-
 def lib():
-    """Load libngp_amd.so (raises if it was not built)."""
+    """Load libngp_amd.so (raises if it was not built) with every entry point's
+    signature as include/ngp_amd.h declares it (capi.py)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise NGPError(f"libngp_amd.so not found at {LIB_PATH}: run `make -C ar-nerf_amd` "
                            "(or __graft_entry__.build()); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
-        _declare(L)
+        capi.declare(L)
         _lib = L
     return _lib
 

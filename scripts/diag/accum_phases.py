@@ -18,6 +18,7 @@ sys.path[:0] = [os.path.join(ROOT, "ar-nerf_amd"), HERE]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import capi  # noqa: E402
 import hashgrid as HG  # noqa: E402
 import synthetic as S  # noqa: E402
 import vren  # noqa: E402
@@ -31,12 +32,8 @@ def main():
     if not os.path.exists(lib_path):
         subprocess.run(["make", "-C", HERE, "libaccdiag.so"], check=True)
     D = ctypes.CDLL(lib_path)
-    vp, i64, ci, cf = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-    P = ctypes.POINTER(HG.ngp_hashgrid_t)
-    D.ngp_hash_binned_plan.argtypes = [vp, i64, vp, vp, P, vp, i64, ci, ci, vp]
-    D.ngp_hash_binned_apply_adam.argtypes = [vp, i64, vp, vp, P, vp, vp, vp, i64, ci, ci, vp, vp, vp, vp, vp, cf, cf,
-                                             cf, vp, cf, vp]
-    D.ngp_diag_acc_stamps.argtypes = [vp, ci]
+    capi.declare(D, strict=False)
+    D.ngp_diag_acc_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int]
     dev = torch.device("cuda")
     scene = S.AnalyticScene(W=800, H=800, n_images=100, scale=0.5)
     gt = scene.gt_images(device=dev)

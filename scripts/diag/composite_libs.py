@@ -8,16 +8,17 @@ import json
 import os
 import sys
 
-import torch
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [os.path.join(ROOT, "ar-nerf_amd")]
+import torch  # noqa: E402
+
+import capi  # noqa: E402
 
 vp = ctypes.c_void_p
 
 
 def declare(L):
-    L.ngp_composite_train_fw.argtypes = [vp, vp, vp, vp, vp, ctypes.c_int64, ctypes.c_float, vp, vp, vp, vp, vp, vp]
-    L.ngp_composite_train_bw.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp,
-                                         ctypes.c_float, vp, vp, vp]
-    L.ngp_composite_train_fw.restype = L.ngp_composite_train_bw.restype = ctypes.c_int
+    capi.declare(L, strict=False)
     return L
 
 

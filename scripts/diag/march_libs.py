@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path[:0] = [os.path.join(ROOT, "ar-nerf_amd")]
 import torch  # noqa: E402
 
+import capi  # noqa: E402
 import ktimer as KT  # noqa: E402
 import synthetic as S  # noqa: E402
 import vren  # noqa: E402
@@ -24,11 +25,7 @@ vp = ctypes.c_void_p
 
 
 def declare(L):
-    L.ngp_march_train_slots.argtypes = [vp, vp, vp, ctypes.c_int64, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float,
-                                        ctypes.c_float, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp, vp]
-    L.ngp_march_train_slots.restype = ctypes.c_int
-    L.ngp_probe_set.argtypes = [vp, vp, ctypes.c_int64]
-    L.ngp_probe_set.restype = ctypes.c_int
+    capi.declare(L, strict=False)
     return L
 
 

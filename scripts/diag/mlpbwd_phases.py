@@ -17,6 +17,7 @@ sys.path[:0] = [os.path.join(ROOT, "ar-nerf_amd"), HERE]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import capi  # noqa: E402
 import hashgrid as HG  # noqa: E402
 import synthetic as S  # noqa: E402
 import vren  # noqa: E402
@@ -30,9 +31,8 @@ def main():
     if not os.path.exists(lib_path):
         subprocess.run(["make", "-C", HERE, "libmlpdiag.so"], check=True)
     D = ctypes.CDLL(lib_path)
-    vp, i64 = ctypes.c_void_p, ctypes.c_int64
-    D.ngp_field_backward_mlp.argtypes = [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
-    D.ngp_diag_bwd_stamps.argtypes = [vp, vp, ctypes.c_int]
+    capi.declare(D, strict=False)
+    D.ngp_diag_bwd_stamps.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
     dev = torch.device("cuda")
     scene = S.AnalyticScene(W=800, H=800, n_images=100, scale=0.5)
     gt = scene.gt_images(device=dev)

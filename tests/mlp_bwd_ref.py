@@ -23,9 +23,11 @@ from types import SimpleNamespace
 
 import numpy as np
 
-RGB_NONE, RGB_RELU = 1, 3  # include/ngp_amd.h NGP_RGB_NONE / NGP_RGB_RELU
+from capi import C
+
+RGB_NONE, RGB_RELU = C["NGP_RGB_NONE"], C["NGP_RGB_RELU"]
 OW = {"W1": (0, 64, 32), "W2": (2048, 16, 64), "W3": (3072, 64, 32), "W4": (5120, 64, 64), "W5": (9216, 16, 64)}
-MLP_PARAMS = 10240
+MLP_PARAMS = C["NGP_MLP_PARAMS"]
 BLOCK_ROWS = 128       # rows per block iteration (CW * 16)
 E_SPREAD = 4           # per-row gradient exponents e_s in 0..E_SPREAD
 ZERO_SHARE = 8         # one row in ZERO_SHARE has an all-zero upstream gradient

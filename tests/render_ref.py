@@ -24,9 +24,10 @@ import torch
 
 import composite_ref as CR
 import oracle as O
+from capi import C
 
 # ------------------------------------------------- mirrored kernel constants
-STATE_WORDS = 8            # include/ngp_amd.h:256 NGP_RENDER_STATE_WORDS
+STATE_WORDS = C["NGP_RENDER_STATE_WORDS"]
 RS_ALIVE0, RS_ALIVE1, RS_SAMPLES, RS_NS, RS_ACTIVE, RS_VALID, RS_TOTAL, RS_ITERS = range(8)  # render.hip:28-29
 NS_MAX = 64                # render.hip:58   N_samples = min(N_rays // N_alive, 64)
 BLOCK = 256                # render.hip:308  __launch_bounds__(256) of every loop kernel

@@ -143,3 +143,140 @@ def test_row_forward_entry_points_check_arguments_without_launching():
     assert Lv.ngp_rays_nonempty(p, 8, None, p, None, None, None) == -1
     assert Lv.ngp_rays_nonempty(p, -1, p, p, None, None, None) == -1
     assert Lv.ngp_rays_nonempty(p, 8, p, None, None, None, None) == -1
+
+
+# ------------------------------------------------ the header as the one description (capi.py)
+import subprocess  # noqa: E402
+import sys  # noqa: E402
+from ctypes import (POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64,  # noqa: E402
+                    c_ulonglong, c_void_p)
+
+import capi  # noqa: E402
+import ktimer  # noqa: E402
+import renderer  # noqa: E402
+import trainer  # noqa: E402
+
+_vp, _P = c_void_p, POINTER(capi.ngp_hashgrid_t)
+# one function of each kind, read off include/ngp_amd.h by hand
+_BY_HAND = {
+    "ngp_morton3d": (c_int, [_vp, c_int64, _vp, _vp]),
+    "ngp_timing_tick_ns": (c_double, []),
+    "ngp_version": (c_char_p, []),
+    "ngp_hash_backward_rep_floats": (c_size_t, [_P, c_int, c_int]),
+    "ngp_hashgrid_levels": (c_uint32, [c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp]),
+    "ngp_render_test_capacity": (c_int64, [c_int64, c_int]),
+    "ngp_guard_hits": (c_ulonglong, []),
+    "ngp_sample_batch": (c_int, [c_uint64, c_uint64, c_int64, _vp, c_int, c_int64, c_int64, _vp, _vp, c_int64, _vp, _vp,
+                                 c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_BY_HAND))
+def test_signature_from_header_equals_the_hand_written_one(name):
+    restype, argtypes = capi.FUNCS[name]
+    assert restype is _BY_HAND[name][0]
+    assert len(argtypes) == len(_BY_HAND[name][1])
+    assert all(a is b for a, b in zip(argtypes, _BY_HAND[name][1])), argtypes
+
+
+def test_every_function_token_of_the_header_is_in_funcs():
+    assert set(_declared()) == set(capi.FUNCS)
+
+
+def test_declare_sets_the_header_signatures_on_the_library():
+    L = vren.lib()
+    for name, (restype, argtypes) in capi.FUNCS.items():
+        f = getattr(L, name)
+        assert f.restype is restype and list(f.argtypes) == argtypes, name
+
+
+def _header(tmp_path, text):
+    p = tmp_path / "h.h"
+    p.write_text(text)
+    return str(p)
+
+
+def test_unmapped_type_raises_and_names_the_function(tmp_path):
+    with pytest.raises(TypeError, match="ngp_takes_long"):
+        capi.parse(_header(tmp_path, "int ngp_fine(int a, void* s);\nint ngp_takes_long(float* p, long n, void* s);\n"))
+    with pytest.raises(TypeError, match="ngp_returns_long"):
+        capi.parse(_header(tmp_path, "long ngp_returns_long(void);\n"))
+
+
+def test_declaration_over_three_lines_with_comments_between_parameters_parses(tmp_path):
+    funcs, _ = capi.parse(_header(tmp_path, """
+/* ngp_in_a_comment(int x) is no declaration */
+size_t ngp_split(const float* xyzs, /* (n,3) f32 */ int64_t n,
+                 const ngp_hashgrid_t* grid,   /* the level table */
+                 float scale, /* > 0 */ unsigned long long seed, void* stream);
+"""))
+    assert list(funcs) == ["ngp_split"]
+    restype, argtypes = funcs["ngp_split"]
+    assert restype is c_size_t
+    assert argtypes == [c_void_p, c_int64, _P, c_float, c_ulonglong, c_void_p]
+
+
+def test_a_declaration_the_parser_cannot_read_raises(tmp_path):
+    with pytest.raises(TypeError, match="ngp_callback"):
+        capi.parse(_header(tmp_path, "int ngp_callback(void (*fn)(int), void* stream);\n"))
+
+
+def test_defines_and_enums_give_the_right_integers(tmp_path):
+    _, consts = capi.parse(_header(tmp_path, """
+#define NGP_GUARD_H
+#define NGP_X (-3)
+#define NGP_Y 0x20   /* hex */
+enum { NGP_A = 0, NGP_B, /* gap */ NGP_C = 7, NGP_D,
+       NGP_N };
+"""))
+    assert consts == {"NGP_X": -3, "NGP_Y": 32, "NGP_A": 0, "NGP_B": 1, "NGP_C": 7, "NGP_D": 8, "NGP_N": 9}
+
+
+def test_python_names_keep_the_values_they_had_as_literals():
+    import mlp_bwd_ref
+    import render_ref
+    assert (trainer.STAT_STRIPES, trainer.STAT_STRIDE) == (32, 16)
+    assert (HG.RGB_SIGMOID, HG.RGB_NONE, HG.RGB_LEAKY_RELU, HG.RGB_RELU) == (0, 1, 2, 3)
+    assert HG.MLP_PARAMS == 10240 and HG.N_LEVELS == 16
+    assert renderer.STATE_WORDS == 8 and render_ref.STATE_WORDS == 8
+    assert ktimer.ProbeTimer.WAVES == 65536
+    assert (mlp_bwd_ref.RGB_NONE, mlp_bwd_ref.RGB_RELU) == (1, 3)
+    assert (capi.C["NGP_OK"], capi.C["NGP_EINVAL"], capi.C["NGP_ERANGE"]) == (0, -1, -2)
+
+
+def test_ktimer_name_lists_have_the_enum_lengths():
+    assert len(ktimer.NAMES) == capi.C["NGP_K_COUNT"]
+    assert len(ktimer.PROBES) == capi.C["NGP_P_COUNT"]
+
+
+def test_hashgrid_structure_equals_the_header_typedef():
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "ngp_amd.h")).read(), flags=re.S)
+    body = re.search(r"typedef\s+struct\s*\{(.*?)\}\s*ngp_hashgrid_t\s*;", hdr, flags=re.S).group(1)
+    ctype = {"int": c_int, "float": c_float, "uint32_t": c_uint32}
+    want = []
+    for stmt in filter(None, (s.strip() for s in body.split(";"))):
+        base, rest = stmt.split(None, 1)
+        for d in rest.split(","):
+            m = re.fullmatch(r"\s*(\w+)\s*(?:\[\s*(\w+)\s*(?:\+\s*(\d+))?\s*\])?\s*", d)
+            name, dim, plus = m.groups()
+            if dim is not None:
+                dim = (int(dim) if dim.isdigit() else capi.C[dim]) + int(plus or 0)
+            want.append((name, ctype[base], dim))
+    got = [(n, t._type_, t._length_) if issubclass(t, ctypes.Array) else (n, t, None)
+           for n, t in capi.ngp_hashgrid_t._fields_]
+    assert got == want
+    assert [n for n, _, _ in got] == ["n_levels", "scales", "res", "offsets", "sizes", "xyz_min", "xyz_max"]
+    assert ctypes.sizeof(capi.ngp_hashgrid_t) == 288
+    assert HG.ngp_hashgrid_t is capi.ngp_hashgrid_t
+
+
+def test_vren_alone_declares_the_field_entry_points():
+    """vren.lib() in a process that never imports hashgrid: the field kernels'
+    signatures are set all the same (one loader, one table)."""
+    code = ("import sys; sys.path.insert(0, sys.argv[1]); import vren; L = vren.lib(); "
+            "assert 'hashgrid' not in sys.modules; "
+            "assert L.ngp_field_forward.argtypes is not None; "
+            "assert L.ngp_hash_binned_apply_adam.argtypes is not None")
+    r = subprocess.run([sys.executable, "-c", code, os.path.dirname(os.path.abspath(vren.__file__))],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
