@@ -12,9 +12,9 @@ All compute goes through libngp_amd.so; nothing here runs on the CPU.
 """
 from __future__ import annotations
 
-import ctypes
+import ctypes  # noqa: F401  (ctypes, c_float, _ptr: names tests and diagnostics reach through this module)
 import math
-from ctypes import c_float, c_void_p
+from ctypes import c_float, c_void_p  # noqa: F401
 
 import numpy as np
 import torch
@@ -28,10 +28,11 @@ RGB_SIGMOID, RGB_NONE, RGB_LEAKY_RELU, RGB_RELU = (C["NGP_RGB_" + m] for m in ("
 MLP_PARAMS = C["NGP_MLP_PARAMS"]
 OW = {"W1": (0, 64, 32), "W2": (2048, 16, 64), "W3": (3072, 64, 32), "W4": (5120, 64, 64), "W5": (9216, 16, 64)}
 
-_lib = vren.lib  # the one loader, under the name this module's callers use
+_lib = vren.lib  # the one loader, under the name this module's callers use (the raw view)
+_K = vren.kernels  # the checked view this module calls through
 
 
-def _ptr(t):
+def _ptr(t):  # (raw-view callers; product code passes tensors)
     return c_void_p(t.data_ptr()) if t is not None else None
 
 
@@ -45,11 +46,8 @@ class HashGrid:
         self.base_resolution, self.per_level_scale = base_resolution, per_level_scale
         d = ngp_hashgrid_t()
         d.n_levels = n_levels
-        self.n_entries = int(_lib().ngp_hashgrid_levels(n_levels, log2_T, base_resolution, c_float(per_level_scale),
-                                                        ctypes.cast(d.scales, c_void_p),
-                                                        ctypes.cast(d.res, c_void_p),
-                                                        ctypes.cast(d.offsets, c_void_p),
-                                                        ctypes.cast(d.sizes, c_void_p)))
+        self.n_entries = int(_K().ngp_hashgrid_levels(n_levels, log2_T, base_resolution, per_level_scale, d.scales,
+                                                      d.res, d.offsets, d.sizes))
         for i in range(3):
             d.xyz_min[i] = -scale
             d.xyz_max[i] = scale
@@ -97,10 +95,8 @@ def field_forward(xyzs, dirs, grid: HashGrid, params16, save_enc=True, n_dev=Non
     rgb = torch.empty(n, 3, device=dev)
     enc = torch.empty(n, 32, dtype=torch.float16, device=dev) if save_enc else None
     h = torch.empty(n, 16, dtype=torch.float16, device=dev) if want_h else None
-    st = _lib().ngp_field_forward_act(_ptr(xyzs), _ptr(dirs), n, _ptr(n_dev), ctypes.byref(grid.desc),
-                                      _ptr(params16[MLP_PARAMS:]), _ptr(params16), _ptr(sig), _ptr(rgb), _ptr(enc),
-                                      _ptr(h), int(rgb_act), vren._stream())
-    vren._ok(st, "ngp_field_forward_act")
+    _K().ngp_field_forward_act(xyzs, dirs, n, n_dev, grid.desc, params16[MLP_PARAMS:], params16, sig, rgb, enc, h,
+                               int(rgb_act), vren._stream())
     return sig, rgb, enc, h
 
 
@@ -111,9 +107,7 @@ def density_forward(xyzs, grid: HashGrid, params16, want_h=False, n_dev=None):
     _check(params16, "params16", torch.float16, grid.n_params)
     sig = torch.empty(n, device=xyzs.device)
     h = torch.empty(n, 16, dtype=torch.float16, device=xyzs.device) if want_h else None
-    st = _lib().ngp_density_forward(_ptr(xyzs), n, _ptr(n_dev), ctypes.byref(grid.desc), _ptr(params16[MLP_PARAMS:]),
-                                    _ptr(params16), _ptr(sig), _ptr(h), vren._stream())
-    vren._ok(st, "ngp_density_forward")
+    _K().ngp_density_forward(xyzs, n, n_dev, grid.desc, params16[MLP_PARAMS:], params16, sig, h, vren._stream())
     return sig, h
 
 
@@ -126,9 +120,7 @@ def density_input_grad(xyzs, grid: HashGrid, params16, dL_dsigma=None):
     if dL_dsigma is not None:
         _check(dL_dsigma, "dL_dsigma", torch.float32)
     out = torch.empty(n, 3, device=xyzs.device)
-    st = _lib().ngp_density_input_grad(_ptr(xyzs), n, ctypes.byref(grid.desc), _ptr(params16[MLP_PARAMS:]),
-                                       _ptr(params16), _ptr(dL_dsigma), _ptr(out), vren._stream())
-    vren._ok(st, "ngp_density_input_grad")
+    _K().ngp_density_input_grad(xyzs, n, grid.desc, params16[MLP_PARAMS:], params16, dL_dsigma, out, vren._stream())
     return out
 
 
@@ -156,12 +148,10 @@ def field_input_grad(xyzs, dirs, grid: HashGrid, params16, enc, dL_drgb, denc, r
     dx = torch.zeros(n, 3, device=xyzs.device)
     dd = torch.zeros(n, 3, device=xyzs.device) if want_dirs else None
     rows = n if sample_idx is None else sample_idx.numel()
-    st = _lib().ngp_field_input_grad(_ptr(xyzs), _ptr(dirs) if want_dirs else None, rows, _ptr(n_dev),
-                                     _ptr(sample_idx), ctypes.byref(grid.desc), _ptr(params16[MLP_PARAMS:]),
-                                     _ptr(params16), _ptr(enc) if want_dirs else None,
-                                     _ptr(dL_drgb) if want_dirs else None, _ptr(denc), int(rgb_act), _ptr(dx),
-                                     _ptr(dd), vren._stream())
-    vren._ok(st, "ngp_field_input_grad")
+    if not want_dirs:
+        dirs = enc = dL_drgb = None
+    _K().ngp_field_input_grad(xyzs, dirs, rows, n_dev, sample_idx, grid.desc, params16[MLP_PARAMS:], params16, enc,
+                              dL_drgb, denc, int(rgb_act), dx, dd, vren._stream())
     return dx, dd
 
 
@@ -174,10 +164,8 @@ def field_backward(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL_drgb, 
     _check(dL_dsig, "dL_dsigmas", torch.float32); _check(dL_drgb, "dL_drgbs", torch.float32)
     if denc_ws is None:
         denc_ws = torch.empty(n, 32, device=xyzs.device)
-    st = _lib().ngp_field_backward_act(_ptr(xyzs), _ptr(dirs), n, _ptr(n_dev), ctypes.byref(grid.desc), _ptr(enc),
-                                       _ptr(params16), _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc_ws), _ptr(grad),
-                                       _ptr(grad[MLP_PARAMS:]), int(rgb_act), vren._stream())
-    vren._ok(st, "ngp_field_backward_act")
+    _K().ngp_field_backward_act(xyzs, dirs, n, n_dev, grid.desc, enc, params16, dL_dsig, dL_drgb, denc_ws, grad,
+                                grad[MLP_PARAMS:], int(rgb_act), vren._stream())
 
 
 BIN_LEVEL_LO, BIN_MERGE_HI = 8, 11  # the trainer's hybrid split on object scenes (trainer.NGPTrainer)
@@ -192,7 +180,7 @@ def _binned_workspace(device):
     one per device, allocated on first use and reused by every drop-in backward."""
     ws = _bin_ws.get(device)
     if ws is None:
-        nbytes = _lib().ngp_hash_backward_binned_workspace(BIN_WS_SAMPLES)
+        nbytes = _K().ngp_hash_backward_binned_workspace(BIN_WS_SAMPLES)
         ws = _bin_ws[device] = torch.empty((nbytes + 255) // 256, 64, dtype=torch.int32, device=device)
     return ws
 
@@ -202,7 +190,7 @@ def _rep_buffer(grid, device):
     key = (device, tuple(grid.offsets))
     rep = _rep_bufs.get(key)
     if rep is None:
-        nrep = _lib().ngp_hash_backward_rep_floats(ctypes.byref(grid.desc), COARSE_REP_LEVELS, COARSE_REP)
+        nrep = _K().ngp_hash_backward_rep_floats(grid.desc, COARSE_REP_LEVELS, COARSE_REP)
         rep = _rep_bufs[key] = torch.zeros(nrep, device=device)
     return rep
 
@@ -236,27 +224,22 @@ def field_backward_sparse(xyzs, dirs, grid: HashGrid, params16, enc, dL_dsig, dL
         z = torch.zeros(0, 3, device=xyzs.device)
         return (z if want_in else None), (z.clone() if want_dirs else None)
     dev = xyzs.device
-    L, s = _lib(), vren._stream()
+    K, s = _K(), vren._stream()
     idx = torch.empty(n, dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int64, device=dev)
-    vren._ok(L.ngp_gradient_rows(_ptr(dL_dsig), _ptr(dL_drgb), n, _ptr(idx), _ptr(cnt), s), "gradient_rows")
+    K.ngp_gradient_rows(dL_dsig, dL_drgb, n, idx, cnt, s)
     denc = torch.empty(n, 32, device=dev)
-    vren._ok(L.ngp_field_backward_mlp_act(_ptr(dirs), n, _ptr(cnt), _ptr(idx), _ptr(enc), 0, _ptr(params16),
-                                          _ptr(dL_dsig), _ptr(dL_drgb), _ptr(denc), _ptr(mlp_grad), int(rgb_act), s),
-             "field_backward_mlp_act")
+    K.ngp_field_backward_mlp_act(dirs, n, cnt, idx, enc, 0, params16, dL_dsig, dL_drgb, denc, mlp_grad, int(rgb_act), s)
     dx = dd = None
     if want_in:
         dx, dd = field_input_grad(xyzs, dirs, grid, params16, enc, dL_drgb, denc, rgb_act=rgb_act, n_dev=cnt,
                                   sample_idx=idx, want_dirs=want_dirs)
     if grad is None:
         return dx, dd
-    gt = grad[MLP_PARAMS:]
-    vren._ok(L.ngp_hash_backward_levels_rep(_ptr(xyzs), n, _ptr(cnt), _ptr(idx), ctypes.byref(grid.desc), _ptr(denc),
-                                            _ptr(gt), 0, BIN_LEVEL_LO, _ptr(_rep_buffer(grid, dev)),
-                                            COARSE_REP_LEVELS, COARSE_REP, 1, s), "hash_backward_levels_rep")
-    vren._ok(L.ngp_hash_backward_binned(_ptr(xyzs), n, _ptr(cnt), _ptr(idx), ctypes.byref(grid.desc), _ptr(denc),
-                                        _ptr(gt), _ptr(_binned_workspace(dev)), BIN_WS_SAMPLES, BIN_LEVEL_LO,
-                                        BIN_MERGE_HI, s), "hash_backward_binned")
+    listed = (xyzs, n, cnt, idx, grid.desc, denc, grad[MLP_PARAMS:])
+    K.ngp_hash_backward_levels_rep(*listed, 0, BIN_LEVEL_LO, _rep_buffer(grid, dev), COARSE_REP_LEVELS, COARSE_REP, 1,
+                                   s)
+    K.ngp_hash_backward_binned(*listed, _binned_workspace(dev), BIN_WS_SAMPLES, BIN_LEVEL_LO, BIN_MERGE_HI, s)
     return dx, dd
 
 

@@ -29,8 +29,7 @@ _UID = itertools.count(1)
 PER_ID = 8  # launches per kernel id per step (segments: one per evaluation round + 1, encode / MLP: one per round, +1 in occupancy updates)
 
 
-def _lib():
-    return vren.lib()
+_K = vren.kernels
 
 
 class KernelTimer:
@@ -51,18 +50,17 @@ class KernelTimer:
         self.span = span
         if span is not None:
             self.begin_mask, self.end_mask = 1 << NAMES.index(span[0]), 1 << NAMES.index(span[1])
-        self.tick_ns = _lib().ngp_timing_tick_ns()
+        self.tick_ns = _K().ngp_timing_tick_ns()
         self.uid = next(_UID)  # graphs captured with this table are keyed by it (never reused)
 
     def arm(self):
-        vren._ok(_lib().ngp_timing_set(self.stamps.data_ptr(), self.step.data_ptr(), self.rows, len(NAMES), PER_ID,
-                                       self.begin_mask, self.end_mask), "timing_set")
+        _K().ngp_timing_set(self.stamps, self.step, self.rows, len(NAMES), PER_ID, self.begin_mask, self.end_mask)
 
     def disarm(self):
         """-> launches per kernel id bracketed since arm()"""
         c = (c_int32 * len(NAMES))()
-        vren._ok(_lib().ngp_timing_counts(c, len(NAMES)), "timing_counts")
-        vren._ok(_lib().ngp_timing_set(None, None, 0, 0, 0, 0, 0), "timing_set")
+        _K().ngp_timing_counts(c, len(NAMES))
+        _K().ngp_timing_set(None, None, 0, 0, 0, 0, 0)
         return list(c)
 
     def reset(self):
@@ -144,11 +142,11 @@ class ProbeTimer:
     WAVES = C["NGP_PROBE_WAVES"]
 
     def __init__(self, step_counter, rows=32, device="cuda"):
-        assert _lib().ngp_probe_count() == len(PROBES)
+        assert _K().ngp_probe_count() == len(PROBES)
         self.step = step_counter
         self.rows = rows
         self.buf = torch.zeros(rows, len(PROBES), self.WAVES, 2, dtype=torch.int64, device=device)
-        self.tick_ns = _lib().ngp_timing_tick_ns()
+        self.tick_ns = _K().ngp_timing_tick_ns()
 
     def reset(self):
         self.buf.zero_()
@@ -156,11 +154,11 @@ class ProbeTimer:
     def arm(self):
         torch.cuda.synchronize()
         self.reset()
-        vren._ok(_lib().ngp_probe_set(self.buf.data_ptr(), self.step.data_ptr(), self.rows), "probe_set")
+        _K().ngp_probe_set(self.buf, self.step, self.rows)
 
     def disarm(self):
         torch.cuda.synchronize()
-        vren._ok(_lib().ngp_probe_set(None, None, 0), "probe_set")
+        _K().ngp_probe_set(None, None, 0)
 
     def spans(self, skip_rows=()):
         """{probe: [(row, ms), ...]} for every row where the probe ran, rows in skip_rows excluded"""

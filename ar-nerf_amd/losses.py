@@ -40,11 +40,9 @@ class _NeRFLossFn(torch.autograd.Function):
     def forward(ctx, rgb, gt, opacity, depth, loss_type, lam_op, lam_depth, grid_scale):
         n = rgb.shape[0]
         l_rgb, l_op, l_dep = torch.empty_like(rgb), torch.empty_like(opacity), torch.empty_like(depth)
-        vren._ok(vren.lib().ngp_nerf_loss_fw(vren._check("rgb", rgb, torch.float32), vren._check("rgb_gt", gt, torch.float32),
-                                             vren._check("opacity", opacity, torch.float32),
-                                             vren._check("depth", depth, torch.float32), n, loss_type, lam_op, lam_depth,
-                                             grid_scale, vren._check("l", l_rgb), vren._check("l", l_op),
-                                             vren._check("l", l_dep), vren._stream()), "nerf_loss_fw")
+        vren._checks(torch.float32, rgb=rgb, rgb_gt=gt, opacity=opacity, depth=depth)
+        vren.kernels().ngp_nerf_loss_fw(rgb, gt, opacity, depth, n, loss_type, lam_op, lam_depth, grid_scale, l_rgb,
+                                        l_op, l_dep, vren._stream())
         ctx.save_for_backward(rgb, gt, opacity, depth)
         ctx.args = (loss_type, lam_op, lam_depth, grid_scale)
         return l_rgb, l_op, l_dep
@@ -54,12 +52,9 @@ class _NeRFLossFn(torch.autograd.Function):
         rgb, gt, opacity, depth = ctx.saved_tensors
         n = rgb.shape[0]
         d_rgb, d_op, d_dep = torch.empty_like(rgb), torch.empty_like(opacity), torch.empty_like(depth)
-        c = lambda t: vren._check("grad", t.contiguous(), torch.float32) if t is not None else None  # noqa: E731
-        vren._ok(vren.lib().ngp_nerf_loss_bw(vren._check("rgb", rgb), vren._check("rgb_gt", gt),
-                                             vren._check("opacity", opacity), vren._check("depth", depth), n,
-                                             *ctx.args, c(g_rgb), c(g_op), c(g_dep), vren._check("d", d_rgb),
-                                             vren._check("d", d_op), vren._check("d", d_dep), vren._stream()),
-                 "nerf_loss_bw")
+        c = lambda t: t.contiguous() if t is not None else None  # noqa: E731
+        vren.kernels().ngp_nerf_loss_bw(rgb, gt, opacity, depth, n, *ctx.args, c(g_rgb), c(g_op), c(g_dep), d_rgb, d_op,
+                                        d_dep, vren._stream())
         return d_rgb, None, d_op, d_dep, None, None, None, None
 
 

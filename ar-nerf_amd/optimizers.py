@@ -28,7 +28,7 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = vren.lib()
+        K = vren.kernels()
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
@@ -52,10 +52,8 @@ class FusedAdam(torch.optim.Optimizer):
                     half = st.get("half")
                     if half is None:
                         half = st["half"] = torch.empty(p.shape, dtype=torch.float16, device=p.device)
-                vren._ok(L.ngp_adam_step(*[vren.c_void_p(t.data_ptr()) for t in
-                                           (p, g, st["exp_avg"], st["exp_avg_sq"], half)],
-                                         p.numel(), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                         st["step"], 1.0, 0, vren._stream()), "FusedAdam")
+                K.ngp_adam_step(p, g, st["exp_avg"], st["exp_avg_sq"], half, p.numel(), float(group["lr"]), float(b1),
+                                float(b2), float(group["eps"]), st["step"], 1.0, 0, vren._stream())
                 # the master changed in place under a raw pointer: bump its version so
                 # autograd / other readers see the write, and mark the shadow current
                 torch.autograd.graph.increment_version(p)

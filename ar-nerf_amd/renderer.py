@@ -21,7 +21,6 @@ bit: tests/test_renderer_gpu.py.
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_float, c_void_p
 
 import torch
 
@@ -33,10 +32,6 @@ MAX_SAMPLES = 1024     # models/rendering.py:7
 NEAR_DISTANCE = 0.01   # models/rendering.py:8
 STATE_WORDS = C["NGP_RENDER_STATE_WORDS"]
 RS_ACTIVE, RS_VALID, RS_TOTAL, RS_ITERS = 4, 5, 6, 7
-
-
-def _p(t):
-    return c_void_p(t.data_ptr())
 
 
 class TestRenderer:
@@ -65,8 +60,7 @@ class TestRenderer:
         # graph A: frame opening + K iterations; graph B (replayed while the loop runs): K_tail
         self.K, self.K_tail, self.use_graphs = int(iters_per_graph), int(iters_tail), bool(use_graphs)
         self.bg = (ctypes.c_float * 3)(*[float(b) for b in bg_rgb])
-        L = vren.lib()
-        self.cap = int(L.ngp_render_test_capacity(self.n_rays, self.min_samples))
+        self.cap = int(vren.kernels().ngp_render_test_capacity(self.n_rays, self.min_samples))
         n, cap = self.n_rays, self.cap
         f = dict(device=dev, dtype=torch.float32)
         self.rays_o = torch.zeros(n, 3, **f)
@@ -87,7 +81,7 @@ class TestRenderer:
         self.sample_idx = torch.zeros(cap, dtype=torch.int32, device=dev)
         self.enc = torch.zeros(8 * cap * 4, dtype=torch.float16, device=dev)  # pair-major (8, cap, 4)
         self.summary = torch.zeros(2 * ((density_bitfield.numel() + 255) // 256), dtype=torch.int32, device=dev)
-        self.n_valid_ptr = c_void_p(self.state.data_ptr() + 8 * RS_VALID)
+        self.n_valid = self.state[RS_VALID:]  # (the valid-sample list's length, where the field kernel reads it)
         self._graphs = {}
         self.last_iterations = 0
         # full-frame camera (render_pose)
@@ -96,29 +90,23 @@ class TestRenderer:
     # ------------------------------------------------------------ pieces
     def _iteration(self, k):
         """One loop iteration (rendering.py:186-236) on the current stream."""
-        L, s, par = vren.lib(), vren._stream(), k & 1
-        vren._ok(L.ngp_render_test_march(_p(self.rays_o), _p(self.rays_d), _p(self.hits_t), self.n_rays,
-                                         _p(self.bitfield), self.cascades, self.grid_size, c_float(self.scale),
-                                         c_float(self.esf), MAX_SAMPLES, self.min_samples, self.max_samples, par,
-                                         _p(self.state), _p(self.alive[par]), _p(self.summary), _p(self.xyzs),
-                                         _p(self.dirs), _p(self.deltas), _p(self.ts), _p(self.n_eff),
-                                         _p(self.sample_idx), s), "render_test_march")
+        K, s, par = vren.kernels(), vren._stream(), k & 1
+        K.ngp_render_test_march(self.rays_o, self.rays_d, self.hits_t, self.n_rays, self.bitfield, self.cascades,
+                                self.grid_size, self.scale, self.esf, MAX_SAMPLES, self.min_samples, self.max_samples,
+                                par, self.state, self.alive[par], self.summary, self.xyzs, self.dirs, self.deltas,
+                                self.ts, self.n_eff, self.sample_idx, s)
         # model(xyzs[valid], dirs[valid]) (rendering.py:204-218): NGP.forward over the list
         # (encode + MLPs in one launch; no encoding kept: nothing goes backward)
-        vren._ok(L.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, self.n_valid_ptr,
-                                            _p(self.sample_idx), ctypes.byref(self.grid.desc),
-                                            _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), None,
-                                            _p(self.sigmas), _p(self.rgbs), None, self.rgb_act, s),
-                 "field_encode_mlp_act")
-        vren._ok(L.ngp_render_test_composite(_p(self.sigmas), _p(self.rgbs), _p(self.deltas), _p(self.ts),
-                                             _p(self.n_eff), self.n_rays, par, _p(self.state), _p(self.alive[par]),
-                                             _p(self.alive[par ^ 1]), c_float(self.T_threshold), _p(self.opacity),
-                                             _p(self.depth), _p(self.rgb), s), "render_test_composite")
+        K.ngp_field_encode_mlp_act(self.xyzs, self.dirs, self.cap, self.n_valid, self.sample_idx, self.grid.desc,
+                                   self.params16[HG.MLP_PARAMS:], self.params16, None, self.sigmas, self.rgbs, None,
+                                   self.rgb_act, s)
+        K.ngp_render_test_composite(self.sigmas, self.rgbs, self.deltas, self.ts, self.n_eff, self.n_rays, par,
+                                    self.state, self.alive[par], self.alive[par ^ 1], self.T_threshold, self.opacity,
+                                    self.depth, self.rgb, s)
 
     def _begin(self):
-        L, s = vren.lib(), vren._stream()
-        vren._ok(L.ngp_render_test_begin(self.n_rays, _p(self.state), _p(self.alive[0]), _p(self.opacity),
-                                         _p(self.depth), _p(self.rgb), s), "render_test_begin")
+        vren.kernels().ngp_render_test_begin(self.n_rays, self.state, self.alive[0], self.opacity, self.depth, self.rgb,
+                                             vren._stream())
         vren.bitfield_summary(self.bitfield, self.grid_size, out=self.summary)
 
     def _run(self, first):
@@ -156,8 +144,7 @@ class TestRenderer:
         if bg_sh is not None:
             vren.render_test_finish_sh(self.opacity, self.rays_d, bg_sh, self.rgb)
         else:
-            vren._ok(vren.lib().ngp_render_test_finish(_p(self.opacity), self.n_rays, self.bg, _p(self.rgb),
-                                                       vren._stream()), "render_test_finish")
+            vren.kernels().ngp_render_test_finish(self.opacity, self.n_rays, self.bg, self.rgb, vren._stream())
         return {"opacity": self.opacity, "depth": self.depth, "rgb": self.rgb,
                 "total_samples": self.state[RS_TOTAL]}
 
@@ -193,10 +180,8 @@ class TestRenderer:
         if self._dirs is None:
             raise RuntimeError("call set_camera() first")
         self._pose.copy_(c2w.reshape(1, 3, 4))
-        vren._ok(vren.lib().ngp_raygen_aabb(_p(self._dirs), _p(self._pose), _p(self._img), _p(self._pix),
-                                            self.n_rays, _p(self._center), _p(self._half), c_float(NEAR_DISTANCE),
-                                            _p(self.rays_o), _p(self.rays_d), _p(self.hits_t), vren._stream()),
-                 "raygen_aabb")
+        vren.kernels().ngp_raygen_aabb(self._dirs, self._pose, self._img, self._pix, self.n_rays, self._center,
+                                       self._half, NEAR_DISTANCE, self.rays_o, self.rays_d, self.hits_t, vren._stream())
         return self.render_loaded()
 
 

@@ -42,8 +42,7 @@ NEAR_DISTANCE = 0.01  # models/rendering.py:10
 LOSS_TYPES = {"raw": 0, "mse": 1, "log": 2, "tanh": 3}
 
 
-def _p(t):
-    return HG._ptr(t)
+_p = HG._ptr  # (diagnostics import it; the trainer passes tensors)
 
 
 STAT_STRIPES, STAT_STRIDE = C["NGP_STAT_STRIPES"], C["NGP_STAT_STRIDE"]
@@ -165,8 +164,9 @@ class NGPTrainer:
         self._occ_key = torch.zeros(self.density_grid.shape, dtype=torch.int64, device=dev)
         self._occ_list = torch.empty(self.G ** 3, dtype=torch.int32, device=dev)
         self._occ_count = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._occ_list_ws = torch.empty((vren.lib().ngp_occupied_cells_workspace(self.G ** 3) + 3) // 4,
-                                        dtype=torch.int32, device=dev)
+        self.L = K = vren.kernels()  # the checked view: tensors and numbers as they are, a failed status raises
+        self._occ_list_ws = torch.empty((K.ngp_occupied_cells_workspace(self.G ** 3) + 3) // 4, dtype=torch.int32,
+                                        device=dev)
         self._occ_xyz = torch.empty(M2, 3, device=dev)
         self._occ_flat = torch.empty(M2, dtype=torch.int64, device=dev)
         self._occ_sig = torch.empty(M2, device=dev)
@@ -177,7 +177,7 @@ class NGPTrainer:
         self._occ_mark = torch.empty((self.G ** 3 + 15) // 16, 4, dtype=torch.int32, device=dev)
         self._occ_kept = torch.empty(M2, dtype=torch.int32, device=dev)
         self._occ_kept_n = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._occ_ws = torch.empty((vren.lib().ngp_occupancy_sorted_workspace(M2 // 2) + 7) // 8, dtype=torch.float64,
+        self._occ_ws = torch.empty((K.ngp_occupancy_sorted_workspace(M2 // 2) + 7) // 8, dtype=torch.float64,
                                    device=dev)
         self.threshold = torch.zeros(2, device=dev)
         # ---- per-step buffers
@@ -239,8 +239,7 @@ class NGPTrainer:
         self.chunk_first = int(chunk_first)
         self.eval_counts = torch.empty(R, dtype=torch.int32, device=dev)
         # round-2 list in one launch (counts + look-back scan + map): its look-back workspace, zeroed once
-        self._cs_ws = torch.zeros((vren.lib().ngp_chunk_segments_workspace(R) + 7) // 8, dtype=torch.int64,
-                                  device=dev)
+        self._cs_ws = torch.zeros((K.ngp_chunk_segments_workspace(R) + 7) // 8, dtype=torch.int64, device=dev)
         # row forward (the default since round 4: +2 %, 9 of 9 alternating pairs,
         # profiles/r04/ab/row_forward_variants.txt): round 1 one wave per non-empty row with the
         # row's transmittance in its epilogue, which appends the row's round-2 samples to the
@@ -283,7 +282,7 @@ class NGPTrainer:
         self.bin_merge_hi = int(bin_merge_hi)
         if hash_backward != "atomic":
             self.bin_max_samples = R * bin_samples_per_ray
-            nbytes = vren.lib().ngp_hash_backward_binned_workspace(self.bin_max_samples)
+            nbytes = K.ngp_hash_backward_binned_workspace(self.bin_max_samples)
             self.bin_ws = torch.empty((nbytes + 255) // 256, 64, dtype=torch.int32, device=dev)
         # coarse atomic levels [0, coarse_rep_levels) add into coarse_rep replicas of their
         # gradient range, folded afterwards (ngp_hash_backward_levels_rep): the coarsest
@@ -294,8 +293,7 @@ class NGPTrainer:
         self.coarse_rep_levels = min(COARSE_REP_LEVELS, self.bin_level_lo) if hash_backward != "atomic" else 0
         self.rep_buf = None
         if self.coarse_rep > 0 and self.coarse_rep_levels > 0:
-            nrep = vren.lib().ngp_hash_backward_rep_floats(HG.ctypes.byref(self.grid.desc), self.coarse_rep_levels,
-                                                           self.coarse_rep)
+            nrep = K.ngp_hash_backward_rep_floats(self.grid.desc, self.coarse_rep_levels, self.coarse_rep)
             self.rep_buf = torch.zeros(nrep, **f)
         self.bg = torch.ones(3, **f) if self.esf == 0 else torch.zeros(3, **f)  # models/rendering.py:287-296
         self._bg_rand = torch.zeros(3, **f)
@@ -322,7 +320,6 @@ class NGPTrainer:
         self.use_graphs = bool(use_graphs)
         self._graphs = {}
         self._graph_post = {}
-        self.L = vren.lib()
         # {"field_fwd"|"mlp_bwd"|"hash_bwd"|stage: (start, end) torch.cuda.Event} (eager diagnostics)
         self.kernel_events = None
         # ktimer.KernelTimer (bench): graph replays carry HIP events around every kernel
@@ -361,6 +358,29 @@ class NGPTrainer:
         for k, v in m.items():
             setattr(self, k, v)
 
+    # ---- argument groups the launches below share, in the header's order
+    @property
+    def _field(self):
+        """(grid, hash table, MLP weights): the field as every kernel that evaluates it takes it"""
+        return self.grid.desc, self.params16[HG.MLP_PARAMS:], self.params16
+
+    @property
+    def _listed(self):
+        """The hash backward's leading arguments: the bound set's gradient-carrying
+        samples (xyzs, capacity, count, list), the grid, dL/denc, the table's gradient"""
+        return (self.xyzs, self.cap, self.n_active_total, self.sample_idx, self.grid.desc, self.denc,
+                self.grad[HG.MLP_PARAMS:])
+
+    @property
+    def _bin(self):
+        """... and the binned levels' (workspace, its sample capacity, level_lo, merge_hi) after them"""
+        return self.bin_ws, self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi
+
+    @property
+    def _adam_hp(self):
+        """FusedAdam's (lr, beta1, beta2, eps, step count, gradient scale 1 / world); lr and the count on the device"""
+        return self.lr_dev, 0.9, 0.999, 1e-15, self.dctr, 1.0 / self.world
+
     # ------------------------------------------------------- pose refinement
     def _pose_state(self, poses):
         """optimize_ext: the trainer's PoseRefiner and its device state, created
@@ -397,8 +417,7 @@ class NGPTrainer:
     def _pose_compose(self, poses):
         """poses_eff = [Rod(dR) R | t + dT] on the current stream (train.py:92-95); `poses` is not modified"""
         ps = self._pose_state(poses)
-        vren._ok(self.L.ngp_pose_compose(_p(poses), _p(ps["ext"]), ps["n_img"], _p(ps["poses_eff"]), vren._stream()),
-                 "pose_compose")
+        self.L.ngp_pose_compose(poses, ps["ext"], ps["n_img"], ps["poses_eff"], vren._stream())
         return ps["poses_eff"]
 
     def _pose_backward(self, directions, poses, apply_adam):
@@ -413,22 +432,18 @@ class NGPTrainer:
         world, and the world is 1 here."""
         ps, L, s, R = self._ps, self.L, vren._stream(), self.batch_size
         self._ev("pose_bwd", 0)
-        vren._ok(L.ngp_field_input_grad_pm(
-            _p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
-            HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), _p(self.enc),
-            self.cap, _p(self.drgb), _p(self.denc), self.rgb_act, _p(ps["dxyz"]), _p(ps["ddir"]), s), "field_input_grad")
+        L.ngp_field_input_grad_pm(self.xyzs, self.dirs, self.cap, self.n_active_total, self.sample_idx, *self._field,
+                                  self.enc, self.cap, self.drgb, self.denc, self.rgb_act, ps["dxyz"], ps["ddir"], s)
         ra = ps["rays_act"]
         ra.copy_(self.rays_a)
         ra[:, 2].copy_(self.n_active)
-        vren._ok(L.ngp_ray_segment_sum(_p(ps["dxyz"]), _p(ps["ddir"]), _p(self.ts), self.cap, _p(ra), R,
-                                       _p(ps["d_rays_o"]), _p(ps["d_rays_d"]), s), "ray_segment_sum")
-        vren._ok(L.ngp_pose_grad(_p(ps["d_rays_o"]), _p(ps["d_rays_d"]), _p(self.img_idxs), _p(self.pix_idxs), R,
-                                 _p(directions), _p(poses), _p(ps["ext"]), ps["n_img"], _p(ps["grad"]), s), "pose_grad")
+        L.ngp_ray_segment_sum(ps["dxyz"], ps["ddir"], self.ts, self.cap, ra, R, ps["d_rays_o"], ps["d_rays_d"], s)
+        L.ngp_pose_grad(ps["d_rays_o"], ps["d_rays_d"], self.img_idxs, self.pix_idxs, R, directions, poses, ps["ext"],
+                        ps["n_img"], ps["grad"], s)
         if apply_adam:
-            vren._ok(L.ngp_adam_step_dev(_p(ps["ext"]), _p(ps["grad"]), _p(ps["m"]), _p(ps["v"]), _p(ps["ext16"]),
-                                         ps["ext"].numel(), _p(ps["lr"]), ctypes_float(0.9), ctypes_float(0.999),
-                                         ctypes_float(1e-8), _p(ps["step"]), ctypes_float(1.0), 0, s), "pose_adam")
-            vren._ok(L.ngp_counters_inc(_p(ps["step"]), 1, s), "pose_counter")
+            L.ngp_adam_step_dev(ps["ext"], ps["grad"], ps["m"], ps["v"], ps["ext16"], ps["ext"].numel(), ps["lr"], 0.9,
+                                0.999, 1e-8, ps["step"], 1.0, 0, s)
+            L.ngp_counters_inc(ps["step"], 1, s)
         self._ev("pose_bwd", 1)
 
     @torch.no_grad()
@@ -487,23 +502,20 @@ class NGPTrainer:
         sc = min(2 ** (c - 1), self.scale)
         half_grid_size = sc / G
         M = G ** 3 // 4
-        vren._ok(L.ngp_occupied_cells(_p(self.density_grid[c]), G ** 3, ctypes_float(density_threshold),
-                                      _p(self._occ_list), _p(self._occ_count), _p(self._occ_list_ws), s),
-                 "occupied_cells")
+        L.ngp_occupied_cells(self.density_grid[c], G ** 3, density_threshold, self._occ_list, self._occ_count,
+                             self._occ_list_ws, s)
         lo, hi = ddp.shard_range(2 * M, self.rank, self.world)
         # (keep: every rank draws the whole list, positions = list positions, so that
         # the kept ones -- a cell's last draw -- are found over the whole list)
         glo, ghi = (0, 2 * M) if self.occ_keep else (lo, hi)
-        args = (self.occ_seed, _p(self.dctr[2:]), c, G, M, ctypes_float(sc - half_grid_size),
-                ctypes_float(half_grid_size), _p(self._occ_list), _p(self._occ_count), glo, ghi)
         # each half's cells drawn in ascending order: the density forward's waves
         # stay cache-local (1.8x faster than draw order, scripts/diag/density_order.py)
-        vren._ok(L.ngp_occupancy_samples_sorted(*args, _p(self._occ_ws), _p(self._occ_xyz),
-                                                _p(self._occ_flat), s), "occupancy_samples_sorted")
+        L.ngp_occupancy_samples_sorted(self.occ_seed, self.dctr[2:], c, G, M, sc - half_grid_size, half_grid_size,
+                                       self._occ_list, self._occ_count, glo, ghi, self._occ_ws, self._occ_xyz,
+                                       self._occ_flat, s)
         if self.occ_keep:
-            vren._ok(L.ngp_occupancy_keep(_p(self._occ_flat), M, c * G ** 3, G ** 3, lo, hi,
-                                          _p(self._occ_mark), _p(self._occ_kept), _p(self._occ_kept_n), s),
-                     "occupancy_keep")
+            L.ngp_occupancy_keep(self._occ_flat, M, c * G ** 3, G ** 3, lo, hi, self._occ_mark, self._occ_kept,
+                                 self._occ_kept_n, s)
         return lo, hi, M
 
     def update_density_grid(self, density_threshold, warmup=False, decay=0.95, erode=None, jitter=None,
@@ -554,30 +566,22 @@ class NGPTrainer:
                 n = hi - lo
                 if self.occ_keep:
                     # encode + density net of the kept samples only (sigma written at their position)
-                    vren._ok(self.L.ngp_field_encode_mlp(_p(self._occ_xyz), None, n, _p(self._occ_kept_n),
-                                                         _p(self._occ_kept), HG.ctypes.byref(self.grid.desc),
-                                                         _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
-                                                         None, _p(self._occ_sig), None, None, s),
-                             "density_encode_mlp")
-                    vren._ok(L.ngp_density_scatter_kept(_p(self._occ_kept), _p(self._occ_kept_n), n,
-                                                        _p(self._occ_flat), _p(self._occ_sig), 0, _p(key), s),
-                             "density_scatter_kept")
+                    L.ngp_field_encode_mlp(self._occ_xyz, None, n, self._occ_kept_n, self._occ_kept, *self._field, None,
+                                           self._occ_sig, None, None, s)
+                    L.ngp_density_scatter_kept(self._occ_kept, self._occ_kept_n, n, self._occ_flat, self._occ_sig, 0,
+                                               key, s)
                     continue
                 # encode + density net in one launch (no encoding kept)
-                vren._ok(self.L.ngp_field_encode_mlp(_p(self._occ_xyz), None, n, None, None,
-                                                     HG.ctypes.byref(self.grid.desc),
-                                                     _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16), None,
-                                                     _p(self._occ_sig), None, None, s), "density_encode_mlp")
+                L.ngp_field_encode_mlp(self._occ_xyz, None, n, None, None, *self._field, None, self._occ_sig, None,
+                                       None, s)
                 sig, flat = self._occ_sig, self._occ_flat
             # density_grid_tmp[c, indices] = sigma, list positions lo + i (rank shards)
-            vren._ok(L.ngp_density_scatter_last(_p(flat), _p(sig), n, lo, _p(key), s), "density_scatter_last")
+            L.ngp_density_scatter_last(flat, sig, n, lo, key, s)
         if not warmup:
-            vren._ok(L.ngp_counters_inc(_p(self.dctr[2:]), 1, s), "counters_inc")
+            L.ngp_counters_inc(self.dctr[2:], 1, s)
         ddp.combine_density_tmp_(key, self.pg)
-        st = L.ngp_density_grid_ema(_p(self.density_grid), _p(key), self.density_grid.numel(), ctypes_float(decay),
-                                    _p(self.decay_cells) if erode else None, ctypes_float(density_threshold),
-                                    _p(self._sum_cnt), _p(self.threshold), s)
-        vren._ok(st, "density_grid_ema")
+        L.ngp_density_grid_ema(self.density_grid, key, self.density_grid.numel(), decay,
+                               self.decay_cells if erode else None, density_threshold, self._sum_cnt, self.threshold, s)
         ddp.sync_threshold_(self.threshold, self.pg)  # identical threshold on every rank
         vren.packbits(self.density_grid, self.threshold[:1], self.density_bitfield)
 
@@ -595,26 +599,24 @@ class NGPTrainer:
         with torch.cuda.stream(stream):
             if side:
                 self._ev("march_side", 0, stream)
-            s = HG.c_void_p(stream.cuda_stream)
+            s = stream.cuda_stream
+            rays = (m["rays_o"], m["rays_d"], m["hits_t"])
             if src[0] == "sample":
                 _, add, gt = src
                 n_img, hw = gt.shape[0], gt.shape[1]
                 assert gt.dtype in (torch.uint8, torch.float32) and gt.is_contiguous()
-                vren._ok(L.ngp_sample_batch_dev(self.sample_seed, _p(self.dctr[1:]), add, self.rank * R, _p(gt),
-                                                int(gt.dtype == torch.float32), n_img, hw,
-                                                _p(directions), _p(poses), R, _p(self.center), _p(self.half_size),
-                                                ctypes_float(NEAR_DISTANCE), _p(m["img_idxs"]), _p(m["pix_idxs"]),
-                                                _p(m["rgb_gt"]), _p(m["noise"]), _p(m["rays_o"]), _p(m["rays_d"]),
-                                                _p(m["hits_t"]), s), "sample_batch")
+                L.ngp_sample_batch_dev(self.sample_seed, self.dctr[1:], add, self.rank * R, gt,
+                                       int(gt.dtype == torch.float32), n_img, hw, directions, poses, R, self.center,
+                                       self.half_size, NEAR_DISTANCE, m["img_idxs"], m["pix_idxs"], m["rgb_gt"],
+                                       m["noise"], *rays, s)
             else:
                 _, img_idxs, pix_idxs, noise = src
                 assert img_idxs.shape[0] == R
                 if self.optimize_ext:  # (the pose gradient reads the batch's indices from the set)
                     m["img_idxs"].copy_(img_idxs)
                     m["pix_idxs"].copy_(pix_idxs)
-                vren._ok(L.ngp_raygen_aabb(_p(directions), _p(poses), _p(img_idxs), _p(pix_idxs), R, _p(self.center),
-                                           _p(self.half_size), ctypes_float(NEAR_DISTANCE), _p(m["rays_o"]),
-                                           _p(m["rays_d"]), _p(m["hits_t"]), s), "raygen")
+                L.ngp_raygen_aabb(directions, poses, img_idxs, pix_idxs, R, self.center, self.half_size, NEAR_DISTANCE,
+                                  *rays, s)
                 if noise is None:
                     torch.rand(R, out=m["noise"], generator=self.gen)  # custom_functions.py:83
                 else:
@@ -622,15 +624,11 @@ class NGPTrainer:
             # the bitfield's block summary, rebuilt per march: any writer of
             # density_bitfield (update_density_grid, tests, tools) stays valid
             vren.bitfield_summary(self.density_bitfield, self.G, out=m["occ_summary"])
-            vren._ok(L.ngp_march_train_slots(_p(m["rays_o"]), _p(m["rays_d"]), _p(m["hits_t"]), R,
-                                             _p(self.density_bitfield), self.cascades, self.G,
-                                             ctypes_float(self.scale), ctypes_float(self.esf), _p(m["noise"]),
-                                             self.max_samples, _p(m["counts"]), _p(m["rays_a"]),
-                                             _p(m["n_samples"]), _p(m["slot_t"]), _p(m["slot_dt"]),
-                                             _p(m["occ_summary"]), s), "march_slots")
-            vren._ok(L.ngp_march_train_compact(_p(m["rays_o"]), _p(m["rays_d"]), _p(m["rays_a"]), R,
-                                               _p(m["slot_t"]), _p(m["slot_dt"]), self.max_samples, _p(m["xyzs"]),
-                                               _p(m["dirs"]), _p(m["deltas"]), _p(m["ts"]), s), "march_compact")
+            L.ngp_march_train_slots(*rays, R, self.density_bitfield, self.cascades, self.G, self.scale, self.esf,
+                                    m["noise"], self.max_samples, m["counts"], m["rays_a"], m["n_samples"], m["slot_t"],
+                                    m["slot_dt"], m["occ_summary"], s)
+            L.ngp_march_train_compact(m["rays_o"], m["rays_d"], m["rays_a"], R, m["slot_t"], m["slot_dt"],
+                                      self.max_samples, m["xyzs"], m["dirs"], m["deltas"], m["ts"], s)
             # round 1 of the chunked forward: the list of each row's first chunk_first samples
             # (counts min(N_r, K) + scan + list in one launch), here beside the previous step
             # instead of at the head of this batch's step; its length eval_total1 is counted
@@ -639,11 +637,9 @@ class NGPTrainer:
             rows = self._rows_fwd(K)
             m["eval1_K"] = K if (K > 0 and R <= 65536 and not rows) else 0
             if m["eval1_K"]:
-                vren._ok(L.ngp_ray_segments_capped(_p(m["rays_a"]), R, K, _p(m["act_start1"]), _p(m["eval_total1"]),
-                                                   None, _p(m["eval_idx1"]), s), "segments_capped")
+                L.ngp_ray_segments_capped(m["rays_a"], R, K, m["act_start1"], m["eval_total1"], None, m["eval_idx1"], s)
             elif rows:
-                vren._ok(L.ngp_rays_nonempty(_p(m["rays_a"]), R, _p(m["rows_ne"]), _p(m["n_rows_ne"]), None,
-                                             _p(m["eval_total2"]), s), "rays_nonempty")
+                L.ngp_rays_nonempty(m["rays_a"], R, m["rows_ne"], m["n_rows_ne"], None, m["eval_total2"], s)
             if side:
                 self._ev("march_side", 1, stream)
 
@@ -878,7 +874,7 @@ class NGPTrainer:
         if self.hash_backward != "atomic":
             self.bwd_stream.wait_stream(cs)
             with torch.cuda.stream(self.bwd_stream):
-                run(("coarse",), self._segment_coarse)
+                run(("coarse",), self._coarse_levels)  # (graph segment on the side stream)
             comm.wait_stream(self.bwd_stream)
             self._bucket_update(0)
             nr = len(self.bin_cuts) - 1
@@ -899,7 +895,7 @@ class NGPTrainer:
             for i in range(len(self.buckets)):
                 self._bucket_update(i)
         cs.wait_stream(comm)
-        vren._ok(self.L.ngp_counters_inc(_p(self.dctr), 2, vren._stream()), "counters_inc")
+        self.L.ngp_counters_inc(self.dctr, 2, vren._stream())
 
     def _replay_pair(self, gt, directions, poses):
         """Two consecutive steady-state steps (no occupancy update at, between
@@ -977,16 +973,9 @@ class NGPTrainer:
     def _coarse_levels(self, fold=True):
         """The atomic coarse hash levels [0, bin_level_lo) on the current stream
         (fold=False: their replicated part stays in rep_buf for the accumulation)."""
-        vren._ok(self.L.ngp_hash_backward_levels_rep(
-            _p(self.xyzs), self.cap, _p(self.n_active_total), _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
-            _p(self.denc), _p(self.grad[HG.MLP_PARAMS:]), 0, self.bin_level_lo,
-            _p(self.rep_buf) if self.rep_buf is not None else None,
-            self.coarse_rep_levels if self.rep_buf is not None else 0, max(1, self.coarse_rep), int(fold),
-            vren._stream()), "hash_backward_levels")
-
-    def _segment_coarse(self):
-        """world > 1 graph segment (side stream): the atomic coarse hash levels."""
-        self._coarse_levels()
+        self.L.ngp_hash_backward_levels_rep(*self._listed, 0, self.bin_level_lo, self.rep_buf,
+                                            self.coarse_rep_levels if self.rep_buf is not None else 0,
+                                            max(1, self.coarse_rep), int(fold), vren._stream())
 
     def _segment_apply(self, r):
         """world > 1 graph segment r (main stream): accumulation of the binned
@@ -994,18 +983,12 @@ class NGPTrainer:
         range's bucket chain on the comm stream); segment 0 first writes the
         binned levels' records."""
         if r == 0:
-            vren._ok(self.L.ngp_hash_binned_write(_p(self.xyzs), self.cap, _p(self.n_active_total),
-                                                  _p(self.sample_idx), HG.ctypes.byref(self.grid.desc), _p(self.denc),
-                                                  _p(self.grad[HG.MLP_PARAMS:]), _p(self.bin_ws),
-                                                  self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi,
-                                                  vren._stream()),
-                     "hash_binned_write")
+            self.L.ngp_hash_binned_write(*self._listed, *self._bin, vren._stream())
         self._accum_levels(self.bin_cuts[r], self.bin_cuts[r + 1])
 
     def _accum_levels(self, lo, hi):
-        vren._ok(self.L.ngp_hash_binned_accum_levels(
-            HG.ctypes.byref(self.grid.desc), _p(self.grad[HG.MLP_PARAMS:]), _p(self.bin_ws), self.bin_max_samples,
-            self.bin_level_lo, self.bin_merge_hi, lo, hi, vren._stream()), "hash_binned_accum_levels")
+        self.L.ngp_hash_binned_accum_levels(self.grid.desc, self.grad[HG.MLP_PARAMS:], *self._bin, lo, hi,
+                                            vren._stream())
 
     def _bucket_update(self, i):
         """On the comm stream: reduce-scatter of gradient bucket i into this
@@ -1013,44 +996,38 @@ class NGPTrainer:
         bucket's local gradient), all-gather of the shard's fp16 shadow.  The
         step runs this for every bucket, so its host path is lean: views and
         launch arguments built once (_bucket_host)."""
-        h = self._bucket_host()[i]
         cs = self.comm_stream
         with torch.cuda.stream(cs):
-            comm = ddp.comm_active(self.pg)
-            if not comm:  # (emulation: this rank's shard of the local gradient)
-                h["shard"].copy_(h["src"])
-            else:
-                ddp.reduce_scatter_(h["full"], h["shard"], self.pg)
-            self._adam_shard(i, HG.c_void_p(cs.cuda_stream), zero=True)
-            if comm:
-                ddp.all_gather_(h["p16full"], h["p16shard"], self.pg)
+            self._reduce_bucket(i)
+            self._adam_shard(i, cs.cuda_stream, zero=True)
+            self._gather_bucket(i)
 
     def _bucket_host(self):
         """per bucket: the tensors its collectives take and the argument tuple
         of its Adam launch (ngp_adam_step_dev_zero minus the stream)"""
         if getattr(self, "_bk", None) is None:
             self._bk = []
-            f = ctypes_float
             for i, ((a, b), (lo, hi)) in enumerate(zip(self.buckets, self.shards)):
-                q = lambda t: _p(t[lo:hi])  # noqa: E731
-                adam = (q(self._pbuf), _p(self._gshard[i]), q(self.exp_avg), q(self.exp_avg_sq), q(self._p16buf),
-                        hi - lo, _p(self.lr_dev), f(0.9), f(0.999), f(1e-15), _p(self.dctr), f(1.0 / self.world), 1,
-                        _p(self._gbuf[a:b]), b - a)
-                self._bk.append({"full": self._gbuf[a:b], "src": self._gbuf[lo:hi], "shard": self._gshard[i],
-                                 "p16full": self._p16buf[a:b], "p16shard": self._p16buf[lo:hi], "adam": adam})
+                h = {"full": self._gbuf[a:b], "src": self._gbuf[lo:hi], "shard": self._gshard[i],
+                     "p16full": self._p16buf[a:b], "p16shard": self._p16buf[lo:hi]}
+                h["adam"] = (self._pbuf[lo:hi], h["shard"], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], h["p16shard"],
+                             hi - lo, *self._adam_hp, 1, h["full"], b - a)
+                self._bk.append(h)
         return self._bk
 
-    def _rs(self, i):
-        (a, b), (lo, hi), gs = self.buckets[i], self.shards[i], self._gshard[i]
+    def _reduce_bucket(self, i):
+        """reduce-scatter (SUM) of gradient bucket i into this rank's shard buffer"""
+        h = self._bucket_host()[i]
         if not ddp.comm_active(self.pg):  # (emulation: this rank's shard of the local gradient)
-            gs.copy_(self._gbuf[lo:hi])
+            h["shard"].copy_(h["src"])
         else:
-            ddp.reduce_scatter_(self._gbuf[a:b], gs, self.pg)
+            ddp.reduce_scatter_(h["full"], h["shard"], self.pg)
 
-    def _ag(self, i):
-        (a, b), (lo, hi) = self.buckets[i], self.shards[i]
+    def _gather_bucket(self, i):
+        """all-gather of bucket i's fp16 shadow from every rank's shard"""
+        h = self._bucket_host()[i]
         if ddp.comm_active(self.pg):  # (emulation: the shard's shadow is in place already)
-            ddp.all_gather_(self._p16buf[a:b], self._p16buf[lo:hi], self.pg)
+            ddp.all_gather_(h["p16full"], h["p16shard"], self.pg)
 
     def _graph_body(self, k, gt, directions, poses, update_after=False):
         self.cur = k
@@ -1064,7 +1041,7 @@ class NGPTrainer:
 
             self._compute(self.rgb_gt, True, fork)
             cs.wait_stream(self.march_stream)
-            vren._ok(self.L.ngp_counters_inc(_p(self.dctr), 2, vren._stream()), "counters_inc")
+            self.L.ngp_counters_inc(self.dctr, 2, vren._stream())
         else:
             thr = 0.01 * MAX_SAMPLES / 3 ** 0.5
             drawn = self.cascades == 1
@@ -1076,7 +1053,7 @@ class NGPTrainer:
                 with torch.cuda.stream(self.march_stream):
                     self._occ_draw(0, thr, vren._stream())
             self._compute(self.rgb_gt, True, None)
-            vren._ok(self.L.ngp_counters_inc(_p(self.dctr), 2, vren._stream()), "counters_inc")
+            self.L.ngp_counters_inc(self.dctr, 2, vren._stream())
             if drawn:
                 cs.wait_stream(self.march_stream)
             self.update_density_grid(thr, warmup=False, drawn=drawn)
@@ -1112,7 +1089,7 @@ class NGPTrainer:
             self._set_lr()
         out = self._compute(rgb_gt, apply_adam, fork)
         if apply_adam:
-            vren._ok(self.L.ngp_counters_inc(_p(self.dctr), 2, vren._stream()), "counters_inc")
+            self.L.ngp_counters_inc(self.dctr, 2, vren._stream())
             self.global_step += 1
         return out
 
@@ -1141,11 +1118,10 @@ class NGPTrainer:
             m = self.msets[self.cur]
             pre = 8 if m["pre_ready"] else 0
             m["pre_ready"] = False
-            vren._ok(L.ngp_field_forward_first_pre_act(
-                _p(self.xyzs), _p(self.dirs), _p(self.deltas), _p(self.rays_a), _p(self.rows_ne), _p(self.n_rows_ne),
-                R, self.cap, ctypes_float(1e-4), HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
-                _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs), None, _p(self.eval_idx),
-                _p(self.eval_total2), _p(self.eval_stats), pre, self.rgb_act, s), "field_forward_first")
+            L.ngp_field_forward_first_pre_act(self.xyzs, self.dirs, self.deltas, self.rays_a, self.rows_ne,
+                                              self.n_rows_ne, R, self.cap, 1e-4, *self._field, self.enc, self.sigmas,
+                                              self.rgbs, None, self.eval_idx, self.eval_total2, self.eval_stats, pre,
+                                              self.rgb_act, s)
             self._ev("hash_encode", 1)
             if fork is not None and at == "r1":
                 # (captured before round 2: round 2 captured first and the march forked from an event
@@ -1158,27 +1134,21 @@ class NGPTrainer:
             if self.eval1_K == K:  # built by this batch's march
                 self._field_indexed(s, self.eval_idx1, self.eval_total1)
             else:
-                vren._ok(L.ngp_chunk_counts(_p(self.rays_a), R, K, None, None, ctypes_float(1e-4),
-                                            _p(self.eval_counts), s), "chunk_counts")
-                vren._ok(L.ngp_ray_segments(_p(self.eval_counts), _p(self.rays_a), R, 0, _p(self.act_start),
-                                            _p(self.eval_total), _p(self.eval_stats), _p(self.eval_idx), s),
-                         "segments")
+                L.ngp_chunk_counts(self.rays_a, R, K, None, None, 1e-4, self.eval_counts, s)
+                L.ngp_ray_segments(self.eval_counts, self.rays_a, R, 0, self.act_start, self.eval_total,
+                                   self.eval_stats, self.eval_idx, s)
                 self._field_indexed(s)
             # second round [K, N_r) of the rows still transparent after K samples: counts, scan
             # and list in one launch (ngp_chunk_segments; the two launches it replaces cost a
             # launch gap and a second pass over rays_a)
-            vren._ok(L.ngp_chunk_segments(_p(self.sigmas), _p(self.deltas), _p(self.rays_a), R, K, 0,
-                                          ctypes_float(1e-4), _p(self._cs_ws), _p(self.act_start),
-                                          _p(self.eval_total), _p(self.eval_stats),
-                                          _p(self.eval_total1) if self.eval1_K == K else None, _p(self.eval_idx), s),
-                     "chunk_segments")
+            L.ngp_chunk_segments(self.sigmas, self.deltas, self.rays_a, R, K, 0, 1e-4, self._cs_ws, self.act_start,
+                                 self.eval_total, self.eval_stats, self.eval_total1 if self.eval1_K == K else None,
+                                 self.eval_idx, s)
             self._field_indexed(s)
         else:  # encode + MLPs in one launch over every marched sample
             self._ev("hash_encode", 0)
-            vren._ok(L.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(self.n_samples), None,
-                                                HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
-                                                _p(self.params16), _p(self.enc), _p(self.sigmas), _p(self.rgbs),
-                                                None, self.rgb_act, s), "field_encode_mlp")
+            L.ngp_field_encode_mlp_act(self.xyzs, self.dirs, self.cap, self.n_samples, None, *self._field, self.enc,
+                                       self.sigmas, self.rgbs, None, self.rgb_act, s)
             self._ev("hash_encode", 1)
         self._ev("field_fwd", 1)
         if fork is not None and at == "fwd":
@@ -1186,22 +1156,18 @@ class NGPTrainer:
         bg = self.bg
         if self.random_bg:  # rendering.py:287-288, one colour per batch, drawn on device (graph-safe)
             bg = self._bg_rand
-            vren._ok(L.ngp_random_bg(self.sample_seed ^ 0x6267, _p(self.dctr[1:]), 0, _p(bg), s), "random_bg")
+            L.ngp_random_bg(self.sample_seed ^ 0x6267, self.dctr[1:], 0, bg, s)
         self._ev("composite_loss", 0)
         self._ev("composite", 0)
-        vren._ok(L.ngp_composite_loss(_p(self.sigmas), _p(self.rgbs), _p(self.deltas), _p(self.ts), _p(self.rays_a), R,
-                                      _p(rgb_gt), _p(bg), self.loss_type, ctypes_float(self.lambda_opacity),
-                                      ctypes_float(self.lambda_depth), ctypes_float(self.lambda_distortion),
-                                      ctypes_float(self.scale), ctypes_float(1e-4),
-                                      _p(self.dsig), _p(self.drgb), _p(self.out_rgb), _p(self.out_op),
-                                      _p(self.out_depth), _p(self.out_loss), _p(self.n_active), None, None, None,
-                                      _p(self.stats), s), "composite_loss")
+        L.ngp_composite_loss(self.sigmas, self.rgbs, self.deltas, self.ts, self.rays_a, R, rgb_gt, bg, self.loss_type,
+                             self.lambda_opacity, self.lambda_depth, self.lambda_distortion, self.scale, 1e-4,
+                             self.dsig, self.drgb, self.out_rgb, self.out_op, self.out_depth, self.out_loss,
+                             self.n_active, None, None, None, self.stats, s)
         self._ev("composite", 1)
         # compacted gradient-carrying samples: scan + map (a per-block atomic reservation inside
         # composite_loss serialises on one address, and an ordered decoupled look-back across its
         # 2048 four-row blocks made the launch 5x longer: both measured slower)
-        vren._ok(L.ngp_active_samples(_p(self.n_active), _p(self.rays_a), R, _p(self.act_start),
-                                      _p(self.n_active_total), _p(self.sample_idx), s), "active_samples")
+        L.ngp_active_samples(self.n_active, self.rays_a, R, self.act_start, self.n_active_total, self.sample_idx, s)
         self._ev("composite_loss", 1)
         cs = torch.cuda.current_stream()
         hybrid = self.hash_backward != "atomic"
@@ -1213,10 +1179,7 @@ class NGPTrainer:
             else:
                 bs.wait_event(after)
             with torch.cuda.stream(bs):
-                vren._ok(L.ngp_hash_binned_plan(_p(self.xyzs), self.cap, _p(self.n_active_total),
-                                                _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
-                                                _p(self.bin_ws), self.bin_max_samples, self.bin_level_lo,
-                                                self.bin_merge_hi, vren._stream()), "hash_binned_plan")
+                L.ngp_hash_binned_plan(*self._listed[:5], *self._bin, vren._stream())  # (no dL/denc, no gradient)
                 ev = torch.cuda.Event()
                 ev.record(bs)
             return ev
@@ -1230,10 +1193,8 @@ class NGPTrainer:
             seg_done = torch.cuda.Event()
             seg_done.record(cs)
         self._ev("mlp_bwd", 0)
-        vren._ok(L.ngp_field_backward_mlp_act(_p(self.dirs), self.cap, _p(self.n_active_total),
-                                              _p(self.sample_idx), _p(self.enc), self.cap, _p(self.params16),
-                                              _p(self.dsig), _p(self.drgb), _p(self.denc), _p(self.grad),
-                                              self.rgb_act, s), "field_backward_mlp")
+        L.ngp_field_backward_mlp_act(self.dirs, self.cap, self.n_active_total, self.sample_idx, self.enc, self.cap,
+                                     self.params16, self.dsig, self.drgb, self.denc, self.grad, self.rgb_act, s)
         self._ev("mlp_bwd", 1)
         if seg_done is not None:
             planned = plan(seg_done)
@@ -1245,7 +1206,7 @@ class NGPTrainer:
             # (world > 1 graph segments: the hash backward runs as two more
             # graphs -- coarse levels on the side stream, binned levels here --
             # so the reduce-scatter of the [MLP | coarse] bucket overlaps the
-            # binned levels; _replay / _segment_coarse / _segment_apply)
+            # binned levels; _replay / _dp_sequence / _segment_apply)
             cs.wait_stream(bs)
             return self.out_loss
         self._ev("hash_bwd", 0)
@@ -1285,10 +1246,8 @@ class NGPTrainer:
                         if pre:
                             # the next batch (marched beside this step) gets its round-1 coarse levels now
                             nx = self.msets[1 - self.cur]
-                            vren._ok(L.ngp_field_encode_first_coarse(
-                                _p(nx["xyzs"]), _p(nx["rays_a"]), _p(nx["rows_ne"]), _p(nx["n_rows_ne"]), R,
-                                self.cap, HG.ctypes.byref(self.grid.desc), _p(self.params16[HG.MLP_PARAMS:]),
-                                _p(self.enc), vren._stream()), "encode_first_coarse")
+                            L.ngp_field_encode_first_coarse(nx["xyzs"], nx["rays_a"], nx["rows_ne"], nx["n_rows_ne"], R,
+                                                            self.cap, *self._field[:2], self.enc, vren._stream())
                             nx["pre_ready"] = True
 
             mlp_done = None
@@ -1302,19 +1261,10 @@ class NGPTrainer:
             if binned:  # (none at bin_level_lo == L: the side stream took every level and its Adam)
                 cs.wait_event(planned)
                 if fused:  # + FusedAdam of the binned levels inside the accumulation
-                    vren._ok(L.ngp_hash_binned_apply_adam(
-                        _p(self.xyzs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
-                        HG.ctypes.byref(self.grid.desc), _p(self.denc), _p(self.grad[t:]), _p(self.bin_ws),
-                        self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi, _p(self.params[t:]),
-                        _p(self.exp_avg[t:]), _p(self.exp_avg_sq[t:]), _p(self.params16[t:]), _p(self.lr_dev),
-                        ctypes_float(0.9), ctypes_float(0.999), ctypes_float(1e-15), _p(self.dctr),
-                        ctypes_float(1.0 / self.world), s), "hash_binned_apply_adam")
+                    L.ngp_hash_binned_apply_adam(*self._listed, *self._bin, self.params[t:], self.exp_avg[t:],
+                                                 self.exp_avg_sq[t:], self.params16[t:], *self._adam_hp, s)
                 else:
-                    vren._ok(L.ngp_hash_binned_apply(_p(self.xyzs), self.cap, _p(self.n_active_total),
-                                                     _p(self.sample_idx), HG.ctypes.byref(self.grid.desc),
-                                                     _p(self.denc), _p(self.grad[t:]), _p(self.bin_ws),
-                                                     self.bin_max_samples, self.bin_level_lo, self.bin_merge_hi, s),
-                             "hash_binned_apply")
+                    L.ngp_hash_binned_apply(*self._listed, *self._bin, s)
                     if adam_split:
                         self._adam(split, self.n_params, s)
             self._ev("hash_binned_apply", 1)
@@ -1325,9 +1275,7 @@ class NGPTrainer:
                 self._ev("hash_bwd", 1)
                 return self.out_loss
         else:
-            vren._ok(L.ngp_hash_backward(_p(self.xyzs), self.cap, _p(self.n_active_total), _p(self.sample_idx),
-                                         HG.ctypes.byref(self.grid.desc),
-                                         _p(self.denc), _p(self.grad[HG.MLP_PARAMS:]), s), "hash_backward")
+            L.ngp_hash_backward(*self._listed, s)
         self._ev("hash_bwd", 1)
         if not self.dp and apply_adam:
             self._ev("adam", 0)
@@ -1347,7 +1295,7 @@ class NGPTrainer:
         xGMI; outside graph captures).  apply_adam=False callers (tests) find
         the summed shards in _gshard."""
         for i in range(len(self.buckets)):
-            self._rs(i)
+            self._reduce_bucket(i)
         self._gbuf.zero_()
 
     def _adam_shards(self):
@@ -1362,12 +1310,12 @@ class NGPTrainer:
         args = self._bucket_host()[i]["adam"]
         if not zero:
             args = args[:-2] + (None, 0)
-        vren._ok(self.L.ngp_adam_step_dev_zero(*args, s), "adam")
+        self.L.ngp_adam_step_dev_zero(*args, s)
 
     def _gather_params16(self):
         """All-gather of the updated fp16 shadow the kernels read."""
         for i in range(len(self.buckets)):
-            self._ag(i)
+            self._gather_bucket(i)
 
     def full_params(self):
         """The fp32 master vector, complete on every rank (world > 1: each rank
@@ -1390,18 +1338,13 @@ class NGPTrainer:
         so far, advanced after the step by ngp_counters_inc.  rep: the coarse
         levels' gradient replicas (unfolded, fold=False) are folded here
         (lo <= MLP_PARAMS, hi past the replicated levels)."""
-        q = lambda t: _p(t[lo:hi])  # noqa: E731
+        args = (*(t[lo:hi] for t in (self.params, self.grad, self.exp_avg, self.exp_avg_sq, self.params16)), hi - lo,
+                *self._adam_hp, 1)
         if rep:
-            vren._ok(self.L.ngp_adam_step_dev_rep(
-                q(self.params), q(self.grad), q(self.exp_avg), q(self.exp_avg_sq), q(self.params16), hi - lo,
-                _p(self.lr_dev), ctypes_float(0.9), ctypes_float(0.999), ctypes_float(1e-15), _p(self.dctr),
-                ctypes_float(1.0 / self.world), 1, _p(self.rep_buf), HG.MLP_PARAMS - lo,
-                2 * self.grid.offsets[self.coarse_rep_levels], self.coarse_rep, s), "adam")
-            return
-        vren._ok(self.L.ngp_adam_step_dev(q(self.params), q(self.grad), q(self.exp_avg), q(self.exp_avg_sq),
-                                          q(self.params16), hi - lo, _p(self.lr_dev), ctypes_float(0.9),
-                                          ctypes_float(0.999), ctypes_float(1e-15), _p(self.dctr),
-                                          ctypes_float(1.0 / self.world), 1, s), "adam")
+            self.L.ngp_adam_step_dev_rep(*args, self.rep_buf, HG.MLP_PARAMS - lo,
+                                         2 * self.grid.offsets[self.coarse_rep_levels], self.coarse_rep, s)
+        else:
+            self.L.ngp_adam_step_dev(*args, s)
 
     def _field_indexed(self, s, idx=None, total=None):
         """Field forward (encode + MLPs in one launch) over the listed samples
@@ -1410,11 +1353,8 @@ class NGPTrainer:
         idx = self.eval_idx if idx is None else idx
         total = self.eval_total if total is None else total
         self._ev("hash_encode", 0)
-        vren._ok(self.L.ngp_field_encode_mlp_act(_p(self.xyzs), _p(self.dirs), self.cap, _p(total),
-                                                 _p(idx), HG.ctypes.byref(self.grid.desc),
-                                                 _p(self.params16[HG.MLP_PARAMS:]), _p(self.params16),
-                                                 _p(self.enc), _p(self.sigmas), _p(self.rgbs), None,
-                                                 self.rgb_act, s), "field_encode_mlp")
+        self.L.ngp_field_encode_mlp_act(self.xyzs, self.dirs, self.cap, total, idx, *self._field, self.enc, self.sigmas,
+                                        self.rgbs, None, self.rgb_act, s)
         self._ev("hash_encode", 1)
 
     # ---------------------------------------------------- test-time render
@@ -1464,6 +1404,6 @@ class NGPTrainer:
         return {"rgb": rgb, "opacity": opacity, "depth": depth, "total_samples": total}
 
 
-def ctypes_float(x):
+def ctypes_float(x):  # (diagnostics; the declared c_float argtype converts the trainer's own floats)
     return HG.c_float(float(x))
 

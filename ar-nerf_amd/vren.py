@@ -31,25 +31,49 @@ import capi
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NGP_AMD_LIB", os.path.join(_HERE, "lib", "libngp_amd.so"))
 
-_lib = None
+_lib = _kernels = None
 
 
 class NGPError(RuntimeError):
-    pass
+    status = None  # the C function's return, when that is what failed
+
+
+def _load(errcheck=None):
+    if not os.path.exists(LIB_PATH):
+        raise NGPError(f"libngp_amd.so not found at {LIB_PATH}: run `make -C ar-nerf_amd` "
+                       "(or __graft_entry__.build()); there is no CPU fallback")
+    L = ctypes.CDLL(LIB_PATH)
+    capi.declare(L, errcheck=errcheck)
+    return L
 
 
 def lib():
-    """Load libngp_amd.so (raises if it was not built) with every entry point's
-    signature as include/ngp_amd.h declares it (capi.py)."""
+    """The raw view of libngp_amd.so (raises if it was not built): every entry
+    point's signature as include/ngp_amd.h declares it (capi.py), the status
+    handed back as the return value (tests, bench, diagnostics)."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise NGPError(f"libngp_amd.so not found at {LIB_PATH}: run `make -C ar-nerf_amd` "
-                           "(or __graft_entry__.build()); there is no CPU fallback")
-        L = ctypes.CDLL(LIB_PATH)
-        capi.declare(L)
-        _lib = L
+        _lib = _load()
     return _lib
+
+
+def _raise_status(rc, fn, args):
+    if rc != 0:
+        e = NGPError(f"{fn.__name__} failed with status {rc}")
+        e.status = rc
+        raise e
+    return rc
+
+
+def kernels():
+    """The checked view, which all product code calls: a second handle on the
+    same loaded library with the same signatures, whose status-returning
+    functions raise NGPError (.status) instead of returning nonzero.  Tensors,
+    Python numbers and grid.desc are passed as they are (capi.POINTER_TO)."""
+    global _kernels
+    if _kernels is None:
+        _kernels = _load(_raise_status)
+    return _kernels
 
 
 def _stream():
@@ -86,7 +110,13 @@ def _check(name, x, dtype=None):
     return c_void_p(x.data_ptr())
 
 
-def _ok(st, what):
+def _checks(dtype, **named):
+    """_check(name, x, dtype) of every name=x, in order"""
+    for name, x in named.items():
+        _check(name, x, dtype)
+
+
+def _ok(st, what):  # (callers of the raw view: tests, diagnostics)
     if st != 0:
         raise NGPError(f"{what} failed with status {st}")
 
@@ -94,16 +124,13 @@ def _ok(st, what):
 # ------------------------------------------------------------------ rays
 def ray_aabb_intersect(rays_o, rays_d, centers, half_sizes, max_hits):
     """intersection.cu:59-100 -> [hit_cnt (N) i32, hits_t (N,max_hits,2), hits_voxel_idx (N,max_hits) i64]"""
-    po, pd = _check("rays_o", rays_o, torch.float32), _check("rays_d", rays_d, torch.float32)
-    pc, ph = _check("centers", centers, torch.float32), _check("half_sizes", half_sizes, torch.float32)
+    _checks(torch.float32, rays_o=rays_o, rays_d=rays_d, centers=centers, half_sizes=half_sizes)
     n, nv = rays_o.shape[0], centers.numel() // 3
     dev = rays_o.device
     cnt = torch.empty(n, dtype=torch.int32, device=dev)
     ht = torch.empty(n, max_hits, 2, dtype=torch.float32, device=dev)
     hv = torch.empty(n, max_hits, dtype=torch.int64, device=dev)
-    _ok(lib().ngp_ray_aabb_intersect(po, pd, n, pc, ph, nv, int(max_hits), c_void_p(cnt.data_ptr()),
-                                     c_void_p(ht.data_ptr()), c_void_p(hv.data_ptr()), _stream()),
-        "ray_aabb_intersect")
+    kernels().ngp_ray_aabb_intersect(rays_o, rays_d, n, centers, half_sizes, nv, int(max_hits), cnt, ht, hv, _stream())
     return [cnt, ht, hv]
 
 
@@ -116,11 +143,11 @@ def raygen_aabb(directions, poses, img_idxs, pix_idxs, center, half_size, near_d
     rays_o = torch.empty(n, 3, device=dev)
     rays_d = torch.empty(n, 3, device=dev)
     hits_t = torch.empty(n, 2, device=dev)
-    _ok(lib().ngp_raygen_aabb(_check("directions", directions, torch.float32), _check("poses", poses, torch.float32),
-                              _check("img_idxs", img_idxs, torch.int64), _check("pix_idxs", pix_idxs, torch.int64), n,
-                              _check("center", center, torch.float32), _check("half_size", half_size, torch.float32),
-                              float(near_distance), c_void_p(rays_o.data_ptr()), c_void_p(rays_d.data_ptr()),
-                              c_void_p(hits_t.data_ptr()), _stream()), "raygen_aabb")
+    _checks(torch.float32, directions=directions, poses=poses)
+    _checks(torch.int64, img_idxs=img_idxs, pix_idxs=pix_idxs)
+    _checks(torch.float32, center=center, half_size=half_size)
+    kernels().ngp_raygen_aabb(directions, poses, img_idxs, pix_idxs, n, center, half_size, float(near_distance),
+                              rays_o, rays_d, hits_t, _stream())
     return rays_o, rays_d, hits_t
 
 
@@ -130,7 +157,7 @@ def probe_rays(pts, dirs, center, half_size, near_distance, out=None):
     `dirs`, one shared (R,3) set or (P,R,3) per probe; AABB + near clamp as
     models/rendering.py:29-31.  Returns rays_o, rays_d (P*R,3) and hits_t
     (P*R,2), written into `out` = (rays_o, rays_d, hits_t) when given."""
-    pp, pd = _check("pts", pts, torch.float32), _check("dirs", dirs, torch.float32)
+    _checks(torch.float32, pts=pts, dirs=dirs)
     if pts.dim() != 2 or pts.shape[1] != 3 or dirs.dim() not in (2, 3) or dirs.shape[-1] != 3:
         raise RuntimeError("pts must be (P,3) and dirs (R,3) or (P,R,3)")
     P, R, per_probe = pts.shape[0], dirs.shape[-2], int(dirs.dim() == 3)
@@ -144,18 +171,10 @@ def probe_rays(pts, dirs, center, half_size, near_distance, out=None):
         _check(name, t, torch.float32)
         if t.numel() != n * k:
             raise RuntimeError(f"{name} must hold {n} rays")
-    _ok(lib().ngp_probe_rays(pp, pd, per_probe, P, R, _check("center", center, torch.float32),
-                             _check("half_size", half_size, torch.float32), float(near_distance),
-                             c_void_p(rays_o.data_ptr()), c_void_p(rays_d.data_ptr()), c_void_p(hits_t.data_ptr()),
-                             _stream()), "probe_rays")
+    _checks(torch.float32, center=center, half_size=half_size)
+    kernels().ngp_probe_rays(pts, dirs, per_probe, P, R, center, half_size, float(near_distance), rays_o, rays_d,
+                             hits_t, _stream())
     return rays_o, rays_d, hits_t
-
-
-def _check_shec(shec):
-    p = _check("shec", shec, torch.float32)
-    if tuple(shec.shape) != (9, 3):
-        raise RuntimeError(f"shec must be (9,3), got {tuple(shec.shape)}")
-    return p
 
 
 def render_test_finish_sh(opacity, rays_d, shec, rgb):
@@ -164,9 +183,11 @@ def render_test_finish_sh(opacity, rays_d, shec, rgb):
     n = opacity.numel()
     if rays_d.numel() != 3 * n or rgb.numel() != 3 * n:
         raise RuntimeError("opacity (N), rays_d (N,3) and rgb (N,3) must agree")
-    _ok(lib().ngp_render_test_finish_sh(_check("opacity", opacity, torch.float32),
-                                        _check("rays_d", rays_d, torch.float32), n, _check_shec(shec),
-                                        _check("rgb", rgb, torch.float32), _stream()), "render_test_finish_sh")
+    _checks(torch.float32, opacity=opacity, rays_d=rays_d, shec=shec)
+    if tuple(shec.shape) != (9, 3):
+        raise RuntimeError(f"shec must be (9,3), got {tuple(shec.shape)}")
+    _check("rgb", rgb, torch.float32)
+    kernels().ngp_render_test_finish_sh(opacity, rays_d, n, shec, rgb, _stream())
     return rgb
 
 
@@ -177,10 +198,9 @@ def probe_sh9_project(rays_d, rgb, opacity=None, rgb_sh=None, trans_sh=None):
     if rays_d.dim() != 3 or rays_d.shape[-1] != 3 or rgb.shape != rays_d.shape:
         raise RuntimeError("rays_d and rgb must be (P,R,3)")
     P, R = rays_d.shape[:2]
-    pd, pc = _check("rays_d", rays_d, torch.float32), _check("rgb", rgb, torch.float32)
-    po = None
+    _checks(torch.float32, rays_d=rays_d, rgb=rgb)
     if opacity is not None:
-        po = _check("opacity", opacity, torch.float32)
+        _check("opacity", opacity, torch.float32)
         if opacity.numel() != P * R:
             raise RuntimeError("opacity must be (P,R)")
         if trans_sh is None:
@@ -192,39 +212,40 @@ def probe_sh9_project(rays_d, rgb, opacity=None, rgb_sh=None, trans_sh=None):
     _check("rgb_sh", rgb_sh, torch.float32)
     if rgb_sh.numel() != P * 27 or (trans_sh is not None and trans_sh.numel() != P * 9):
         raise RuntimeError("rgb_sh must be (P,9,3) and trans_sh (P,9)")
-    pt = _check("trans_sh", trans_sh, torch.float32) if trans_sh is not None else None
-    _ok(lib().ngp_probe_sh9_project(pd, pc, po, P, R, c_void_p(rgb_sh.data_ptr()), pt, _stream()),
-        "probe_sh9_project")
+    if trans_sh is not None:
+        _check("trans_sh", trans_sh, torch.float32)
+    kernels().ngp_probe_sh9_project(rays_d, rgb, opacity, P, R, rgb_sh, trans_sh, _stream())
     return rgb_sh, trans_sh
 
 
 # -------------------------------------------------------- occupancy grid
 def morton3D(coords):
-    p = _check("coords", coords, torch.int32)
+    _check("coords", coords, torch.int32)
     out = torch.empty(coords.shape[0], dtype=torch.int32, device=coords.device)
-    _ok(lib().ngp_morton3d(p, coords.shape[0], c_void_p(out.data_ptr()), _stream()), "morton3D")
+    kernels().ngp_morton3d(coords, coords.shape[0], out, _stream())
     return out
 
 
 def morton3D_invert(indices):
-    p = _check("indices", indices, torch.int32)
+    _check("indices", indices, torch.int32)
     out = torch.empty(indices.shape[0], 3, dtype=torch.int32, device=indices.device)
-    _ok(lib().ngp_morton3d_invert(p, indices.shape[0], c_void_p(out.data_ptr()), _stream()), "morton3D_invert")
+    kernels().ngp_morton3d_invert(indices, indices.shape[0], out, _stream())
     return out
 
 
 def packbits(density_grid, density_threshold, density_bitfield):
     """In place on density_bitfield.  density_threshold may be a float or a
     1-element device tensor (then no host sync is needed)."""
-    pg = _check("density_grid", density_grid, torch.float32)
-    pb = _check("density_bitfield", density_bitfield, torch.uint8)
+    _check("density_grid", density_grid, torch.float32)
+    _check("density_bitfield", density_bitfield, torch.uint8)
     if density_grid.numel() != 8 * density_bitfield.numel():
         raise RuntimeError("density_grid must hold 8 cells per bitfield byte")
     if isinstance(density_threshold, torch.Tensor):
-        thr_dev, thr = _check("density_threshold", density_threshold, torch.float32), 0.0
+        _check("density_threshold", density_threshold, torch.float32)
+        thr_dev, thr = density_threshold, 0.0
     else:
         thr_dev, thr = None, float(density_threshold)
-    _ok(lib().ngp_packbits(pg, density_bitfield.numel(), thr, thr_dev, pb, _stream()), "packbits")
+    kernels().ngp_packbits(density_grid, density_bitfield.numel(), thr, thr_dev, density_bitfield, _stream())
 
 
 def bitfield_summary(density_bitfield, grid_size=128, out=None):
@@ -232,11 +253,11 @@ def bitfield_summary(density_bitfield, grid_size=128, out=None):
     of the bitfield != 0), then the same dilated by one 4^3 block.  The
     marchers keep it in LDS to skip empty blocks without a global load and
     rays that pass no occupied block (same results with or without it)."""
-    pb = _check("density_bitfield", density_bitfield, torch.uint8)
+    _check("density_bitfield", density_bitfield, torch.uint8)
     n = density_bitfield.numel()
     if out is None:
         out = torch.empty(2 * ((n + 255) // 256), dtype=torch.int32, device=density_bitfield.device)
-    _ok(lib().ngp_bitfield_summary(pb, n, int(grid_size), c_void_p(out.data_ptr()), _stream()), "bitfield_summary")
+    kernels().ngp_bitfield_summary(density_bitfield, n, int(grid_size), out, _stream())
     return out
 
 
@@ -249,6 +270,16 @@ def _summary_arg(density_bitfield, cascades, grid_size):
 
 
 # ----------------------------------------------------------- marching
+def _march_args(rays_o, rays_d, hits_t, density_bitfield, cascades, scale, exp_step_factor, noise, grid_size,
+                max_samples):
+    """The training marchers' shared leading arguments, checked"""
+    _checks(torch.float32, rays_o=rays_o, rays_d=rays_d, hits_t=hits_t)
+    _check("density_bitfield", density_bitfield, torch.uint8)
+    _check("noise", noise, torch.float32)
+    return (rays_o, rays_d, hits_t, rays_o.shape[0], density_bitfield, int(cascades), int(grid_size), float(scale),
+            float(exp_step_factor), noise, int(max_samples))
+
+
 def march_train_count(rays_o, rays_d, hits_t, density_bitfield, cascades, scale, exp_step_factor, noise,
                       grid_size, max_samples):
     """Pass 1 -> (counts i32 (N), rays_a i64 (N,3) ray-ordered, total i64 (1)), no host sync."""
@@ -257,27 +288,20 @@ def march_train_count(rays_o, rays_d, hits_t, density_bitfield, cascades, scale,
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     rays_a = torch.empty(n, 3, dtype=torch.int64, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
-    _ok(lib().ngp_march_train_count(_check("rays_o", rays_o, torch.float32), _check("rays_d", rays_d, torch.float32),
-                                    _check("hits_t", hits_t, torch.float32), n,
-                                    _check("density_bitfield", density_bitfield, torch.uint8), int(cascades),
-                                    int(grid_size), float(scale), float(exp_step_factor),
-                                    _check("noise", noise, torch.float32), int(max_samples),
-                                    c_void_p(counts.data_ptr()), c_void_p(rays_a.data_ptr()),
-                                    c_void_p(total.data_ptr()), _stream()), "march_train_count")
+    kernels().ngp_march_train_count(*_march_args(rays_o, rays_d, hits_t, density_bitfield, cascades, scale,
+                                                 exp_step_factor, noise, grid_size, max_samples),
+                                    counts, rays_a, total, _stream())
     return counts, rays_a, total
 
 
 def march_train_write(rays_o, rays_d, hits_t, density_bitfield, cascades, scale, exp_step_factor, noise,
                       grid_size, max_samples, rays_a, xyzs, dirs, deltas, ts):
     """Pass 2 into caller buffers (capacity >= total)."""
-    _ok(lib().ngp_march_train_write(_check("rays_o", rays_o, torch.float32), _check("rays_d", rays_d, torch.float32),
-                                    _check("hits_t", hits_t, torch.float32), rays_o.shape[0],
-                                    _check("density_bitfield", density_bitfield, torch.uint8), int(cascades),
-                                    int(grid_size), float(scale), float(exp_step_factor),
-                                    _check("noise", noise, torch.float32), int(max_samples),
-                                    _check("rays_a", rays_a, torch.int64), _check("xyzs", xyzs, torch.float32),
-                                    _check("dirs", dirs, torch.float32), _check("deltas", deltas, torch.float32),
-                                    _check("ts", ts, torch.float32), _stream()), "march_train_write")
+    args = _march_args(rays_o, rays_d, hits_t, density_bitfield, cascades, scale, exp_step_factor, noise, grid_size,
+                       max_samples)
+    _check("rays_a", rays_a, torch.int64)
+    _checks(torch.float32, xyzs=xyzs, dirs=dirs, deltas=deltas, ts=ts)
+    kernels().ngp_march_train_write(*args, rays_a, xyzs, dirs, deltas, ts, _stream())
 
 
 def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades, scale, exp_step_factor, noise,
@@ -293,26 +317,19 @@ def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades, scale,
     total = torch.empty(1, dtype=torch.int64, device=dev)
     slot_t = torch.empty(n * int(max_samples), device=dev)
     slot_dt = torch.empty(n * int(max_samples), device=dev)
-    po, pd = _check("rays_o", rays_o, torch.float32), _check("rays_d", rays_d, torch.float32)
+    args = _march_args(rays_o, rays_d, hits_t, density_bitfield, cascades, scale, exp_step_factor, noise, grid_size,
+                       max_samples)
     summ = _summary_arg(density_bitfield, cascades, grid_size)
-    _ok(lib().ngp_march_train_slots(po, pd, _check("hits_t", hits_t, torch.float32), n,
-                                    _check("density_bitfield", density_bitfield, torch.uint8), int(cascades),
-                                    int(grid_size), float(scale), float(exp_step_factor),
-                                    _check("noise", noise, torch.float32), int(max_samples),
-                                    c_void_p(counts.data_ptr()), c_void_p(rays_a.data_ptr()),
-                                    c_void_p(total.data_ptr()), c_void_p(slot_t.data_ptr()),
-                                    c_void_p(slot_dt.data_ptr()), c_void_p(summ.data_ptr()) if summ is not None else None,
-                                    _stream()), "march_train_slots")
+    K = kernels()
+    K.ngp_march_train_slots(*args, counts, rays_a, total, slot_t, slot_dt, summ, _stream())
     N = int(total.item())
     xyzs = torch.empty(N, 3, device=dev)
     dirs = torch.empty(N, 3, device=dev)
     deltas = torch.empty(N, device=dev)
     ts = torch.empty(N, device=dev)
     if N > 0:
-        _ok(lib().ngp_march_train_compact(po, pd, c_void_p(rays_a.data_ptr()), n, c_void_p(slot_t.data_ptr()),
-                                          c_void_p(slot_dt.data_ptr()), int(max_samples), c_void_p(xyzs.data_ptr()),
-                                          c_void_p(dirs.data_ptr()), c_void_p(deltas.data_ptr()),
-                                          c_void_p(ts.data_ptr()), _stream()), "march_train_compact")
+        K.ngp_march_train_compact(rays_o, rays_d, rays_a, n, slot_t, slot_dt, int(max_samples), xyzs, dirs, deltas, ts,
+                                  _stream())
     counter = torch.stack([total[0].to(torch.int32), torch.full_like(total[0], n, dtype=torch.int32)])
     return [rays_a, xyzs, dirs, deltas, ts, counter]
 
@@ -328,13 +345,12 @@ def raymarching_test(rays_o, rays_d, hits_t, alive_indices, density_bitfield, ca
     ts = torch.empty(n, N_samples, device=dev)
     neff = torch.empty(n, dtype=torch.int32, device=dev)
     summ = _summary_arg(density_bitfield, cascades, grid_size)
-    _ok(lib().ngp_march_test(_check("rays_o", rays_o, torch.float32), _check("rays_d", rays_d, torch.float32),
-                             _check("hits_t", hits_t, torch.float32), _check("alive_indices", alive_indices, torch.int64),
-                             n, _check("density_bitfield", density_bitfield, torch.uint8), int(cascades),
-                             int(grid_size), float(scale), float(exp_step_factor), int(N_samples), int(max_samples),
-                             c_void_p(xyzs.data_ptr()), c_void_p(dirs.data_ptr()), c_void_p(deltas.data_ptr()),
-                             c_void_p(ts.data_ptr()), c_void_p(neff.data_ptr()),
-                             c_void_p(summ.data_ptr()) if summ is not None else None, _stream()), "raymarching_test")
+    _checks(torch.float32, rays_o=rays_o, rays_d=rays_d, hits_t=hits_t)
+    _check("alive_indices", alive_indices, torch.int64)
+    _check("density_bitfield", density_bitfield, torch.uint8)
+    kernels().ngp_march_test(rays_o, rays_d, hits_t, alive_indices, n, density_bitfield, int(cascades), int(grid_size),
+                             float(scale), float(exp_step_factor), int(N_samples), int(max_samples), xyzs, dirs,
+                             deltas, ts, neff, summ, _stream())
     return [xyzs, dirs, deltas, ts, neff]
 
 
@@ -348,12 +364,10 @@ def composite_train_fw(sigmas, rgbs, deltas, ts, rays_a, T_threshold):
     rgb = torch.empty(nr, 3, device=dev)
     ws = torch.empty(N, device=dev)
     tot = torch.empty(nr, dtype=torch.int64, device=dev)
-    _ok(lib().ngp_composite_train_fw(_check("sigmas", sigmas, torch.float32), _check("rgbs", rgbs, torch.float32),
-                                     _check("deltas", deltas, torch.float32), _check("ts", ts, torch.float32),
-                                     _check("rays_a", rays_a, torch.int64), nr, float(T_threshold),
-                                     c_void_p(tot.data_ptr()), c_void_p(op.data_ptr()), c_void_p(dep.data_ptr()),
-                                     c_void_p(rgb.data_ptr()), c_void_p(ws.data_ptr()), _stream()),
-        "composite_train_fw")
+    _checks(torch.float32, sigmas=sigmas, rgbs=rgbs, deltas=deltas, ts=ts)
+    _check("rays_a", rays_a, torch.int64)
+    kernels().ngp_composite_train_fw(sigmas, rgbs, deltas, ts, rays_a, nr, float(T_threshold), tot, op, dep, rgb, ws,
+                                     _stream())
     return [tot, op, dep, rgb, ws]
 
 
@@ -364,14 +378,12 @@ def composite_train_bw(dL_dopacity, dL_ddepth, dL_drgb, dL_dws, sigmas, rgbs, ws
     dev = sigmas.device
     dsig = torch.empty(N, device=dev)
     drgbs = torch.empty(N, 3, device=dev)
-    _ok(lib().ngp_composite_train_bw(
-        _check("dL_dopacity", dL_dopacity, torch.float32), _check("dL_ddepth", dL_ddepth, torch.float32),
-        _check("dL_drgb", dL_drgb, torch.float32), _check("dL_dws", dL_dws, torch.float32),
-        _check("sigmas", sigmas, torch.float32), _check("rgbs", rgbs, torch.float32), _check("ws", ws, torch.float32),
-        _check("deltas", deltas, torch.float32), _check("ts", ts, torch.float32), _check("rays_a", rays_a, torch.int64),
-        nr, _check("opacity", opacity, torch.float32), _check("depth", depth, torch.float32),
-        _check("rgb", rgb, torch.float32), float(T_threshold), c_void_p(dsig.data_ptr()), c_void_p(drgbs.data_ptr()),
-        _stream()), "composite_train_bw")
+    _checks(torch.float32, dL_dopacity=dL_dopacity, dL_ddepth=dL_ddepth, dL_drgb=dL_drgb, dL_dws=dL_dws, sigmas=sigmas,
+            rgbs=rgbs, ws=ws, deltas=deltas, ts=ts)
+    _check("rays_a", rays_a, torch.int64)
+    _checks(torch.float32, opacity=opacity, depth=depth, rgb=rgb)
+    kernels().ngp_composite_train_bw(dL_dopacity, dL_ddepth, dL_drgb, dL_dws, sigmas, rgbs, ws, deltas, ts, rays_a, nr,
+                                     opacity, depth, rgb, float(T_threshold), dsig, drgbs, _stream())
     return [dsig, drgbs]
 
 
@@ -388,11 +400,12 @@ def ray_segment_sum(dL_dxyzs, dL_ddirs, ts, rays_a, n_rays=None):
     dev = dL_dxyzs.device
     do = torch.zeros(nr, 3, device=dev)
     dd = torch.zeros(nr, 3, device=dev)
-    _ok(lib().ngp_ray_segment_sum(
-        _check("dL_dxyzs", dL_dxyzs, torch.float32),
-        _check("dL_ddirs", dL_ddirs, torch.float32) if dL_ddirs is not None else None,
-        _check("ts", ts, torch.float32), N, _check("rays_a", rays_a, torch.int64), rays_a.shape[0],
-        c_void_p(do.data_ptr()), c_void_p(dd.data_ptr()), _stream()), "ray_segment_sum")
+    _check("dL_dxyzs", dL_dxyzs, torch.float32)
+    if dL_ddirs is not None:
+        _check("dL_ddirs", dL_ddirs, torch.float32)
+    _check("ts", ts, torch.float32)
+    _check("rays_a", rays_a, torch.int64)
+    kernels().ngp_ray_segment_sum(dL_dxyzs, dL_ddirs, ts, N, rays_a, rays_a.shape[0], do, dd, _stream())
     return [do, dd]
 
 
@@ -401,12 +414,12 @@ def composite_test_fw(sigmas, rgbs, deltas, ts, hits_t, alive_indices, T_thresho
     """volumerendering.cu:251-284; alive/opacity/depth/rgb updated in place."""
     n = alive_indices.shape[0]
     Ns = sigmas.shape[1] if sigmas.dim() == 2 else 1
-    _ok(lib().ngp_composite_test_fw(_check("sigmas", sigmas, torch.float32), _check("rgbs", rgbs, torch.float32),
-                                    _check("deltas", deltas, torch.float32), _check("ts", ts, torch.float32), n, Ns,
-                                    _check("alive_indices", alive_indices, torch.int64), float(T_threshold),
-                                    _check("N_eff_samples", N_eff_samples, torch.int32),
-                                    _check("opacity", opacity, torch.float32), _check("depth", depth, torch.float32),
-                                    _check("rgb", rgb, torch.float32), _stream()), "composite_test_fw")
+    _checks(torch.float32, sigmas=sigmas, rgbs=rgbs, deltas=deltas, ts=ts)
+    _check("alive_indices", alive_indices, torch.int64)
+    _check("N_eff_samples", N_eff_samples, torch.int32)
+    _checks(torch.float32, opacity=opacity, depth=depth, rgb=rgb)
+    kernels().ngp_composite_test_fw(sigmas, rgbs, deltas, ts, n, Ns, alive_indices, float(T_threshold), N_eff_samples,
+                                    opacity, depth, rgb, _stream())
 
 
 def ray_sphere_intersect(*args, **kwargs):
@@ -417,25 +430,23 @@ def ray_sphere_intersect(*args, **kwargs):
 def distortion_loss_fw(ws, deltas, ts, rays_a):
     """losses.cu:62-107 -> [loss (N_rays), ws_inclusive_scan (N), wts_inclusive_scan (N)]
     (zero-initialised like the reference's torch::zeros outputs)."""
-    pw, pd, pt = (_check("ws", ws, torch.float32), _check("deltas", deltas, torch.float32),
-                  _check("ts", ts, torch.float32))
-    pr = _check("rays_a", rays_a, torch.int64)
+    _checks(torch.float32, ws=ws, deltas=deltas, ts=ts)
+    _check("rays_a", rays_a, torch.int64)
     nr, N = rays_a.shape[0], ws.shape[0]
     loss = torch.zeros(nr, device=ws.device)
     wsi, wtsi = torch.zeros(N, device=ws.device), torch.zeros(N, device=ws.device)
-    _ok(lib().ngp_distortion_loss_fw(pw, pd, pt, pr, nr, c_void_p(loss.data_ptr()), c_void_p(wsi.data_ptr()),
-                                     c_void_p(wtsi.data_ptr()), _stream()), "distortion_loss_fw")
+    kernels().ngp_distortion_loss_fw(ws, deltas, ts, rays_a, nr, loss, wsi, wtsi, _stream())
     return [loss, wsi, wtsi]
 
 
 def distortion_loss_bw(dL_dloss, ws_inclusive_scan, wts_inclusive_scan, ws, deltas, ts, rays_a):
     """losses.cu:143-173 -> dL_dws (N)"""
-    a = [_check("dL_dloss", dL_dloss, torch.float32), _check("ws_inclusive_scan", ws_inclusive_scan, torch.float32),
-         _check("wts_inclusive_scan", wts_inclusive_scan, torch.float32), _check("ws", ws, torch.float32),
-         _check("deltas", deltas, torch.float32), _check("ts", ts, torch.float32),
-         _check("rays_a", rays_a, torch.int64)]
+    _checks(torch.float32, dL_dloss=dL_dloss, ws_inclusive_scan=ws_inclusive_scan,
+            wts_inclusive_scan=wts_inclusive_scan, ws=ws, deltas=deltas, ts=ts)
+    _check("rays_a", rays_a, torch.int64)
     dws = torch.zeros(ws.shape[0], device=ws.device)
-    _ok(lib().ngp_distortion_loss_bw(*a, rays_a.shape[0], c_void_p(dws.data_ptr()), _stream()), "distortion_loss_bw")
+    kernels().ngp_distortion_loss_bw(dL_dloss, ws_inclusive_scan, wts_inclusive_scan, ws, deltas, ts, rays_a,
+                                     rays_a.shape[0], dws, _stream())
     return dws
 
 
@@ -450,8 +461,7 @@ def density_scatter_last(tmp, indices, sigmas):
     idx = indices.reshape(-1).long().contiguous()
     sig = sigmas.reshape(-1).float().contiguous()
     key = torch.zeros(tmp.numel(), dtype=torch.int64, device=tmp.device)
-    _ok(lib().ngp_density_scatter_last(idx.data_ptr(), sig.data_ptr(), idx.numel(), 0, key.data_ptr(), _stream()),
-        "density_scatter_last")
+    kernels().ngp_density_scatter_last(idx, sig, idx.numel(), 0, key, _stream())
     hit = key != 0
     val = (key & 0xFFFFFFFF).to(torch.int32).view(torch.float32)
     flat = tmp.view(-1)

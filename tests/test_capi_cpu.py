@@ -156,18 +156,19 @@ import ktimer  # noqa: E402
 import renderer  # noqa: E402
 import trainer  # noqa: E402
 
-_vp, _P = c_void_p, POINTER(capi.ngp_hashgrid_t)
-# one function of each kind, read off include/ngp_amd.h by hand
+_vp, _P = capi.POINTER_TO["void"], POINTER(capi.ngp_hashgrid_t)
+_fp, _i64p, _i32p, _u32p = (capi.POINTER_TO[t] for t in ("float", "int64_t", "int32_t", "uint32_t"))
+# one function of each kind, read off include/ngp_amd.h by hand (pointers keep their pointee type)
 _BY_HAND = {
-    "ngp_morton3d": (c_int, [_vp, c_int64, _vp, _vp]),
+    "ngp_morton3d": (c_int, [_i32p, c_int64, _i32p, _vp]),
     "ngp_timing_tick_ns": (c_double, []),
     "ngp_version": (c_char_p, []),
     "ngp_hash_backward_rep_floats": (c_size_t, [_P, c_int, c_int]),
-    "ngp_hashgrid_levels": (c_uint32, [c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp]),
+    "ngp_hashgrid_levels": (c_uint32, [c_int, c_int, c_int, c_float, _fp, _u32p, _u32p, _u32p]),
     "ngp_render_test_capacity": (c_int64, [c_int64, c_int]),
     "ngp_guard_hits": (c_ulonglong, []),
-    "ngp_sample_batch": (c_int, [c_uint64, c_uint64, c_int64, _vp, c_int, c_int64, c_int64, _vp, _vp, c_int64, _vp, _vp,
-                                 c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ngp_sample_batch": (c_int, [c_uint64, c_uint64, c_int64, _vp, c_int, c_int64, c_int64, _fp, _fp, c_int64, _fp, _fp,
+                                 c_float, _i64p, _i64p, _fp, _fp, _fp, _fp, _fp, _vp]),
 }
 
 
@@ -213,7 +214,7 @@ size_t ngp_split(const float* xyzs, /* (n,3) f32 */ int64_t n,
     assert list(funcs) == ["ngp_split"]
     restype, argtypes = funcs["ngp_split"]
     assert restype is c_size_t
-    assert argtypes == [c_void_p, c_int64, _P, c_float, c_ulonglong, c_void_p]
+    assert argtypes == [_fp, c_int64, _P, c_float, c_ulonglong, _vp]
 
 
 def test_a_declaration_the_parser_cannot_read_raises(tmp_path):
@@ -280,3 +281,112 @@ def test_vren_alone_declares_the_field_entry_points():
     r = subprocess.run([sys.executable, "-c", code, os.path.dirname(os.path.abspath(vren.__file__))],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+# ------------------------------------------------ typed pointer parameters, the checked view
+_POINTEES = ("float", "int64_t", "int32_t", "uint8_t", "uint32_t", "uint64_t", "void")
+
+
+def test_pointer_parameter_classes_tally_with_the_header():
+    """Pointer parameters per pointee type, counted from the header text with a
+    regex of this test's own, against the parameter classes in capi.FUNCS."""
+    hdr = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "ngp_amd.h")).read(), flags=re.S)
+    hdr = re.sub(r"^[ \t]*#.*$", "", hdr, flags=re.M)
+    want = dict.fromkeys(_POINTEES, 0)
+    for params in re.findall(r"\bngp_\w+\s*\(([^()]*)\)\s*;", hdr):
+        for base in re.findall(r"(?:const\s+)?(\w+)\s*\*", params):
+            if base not in ("ngp_hashgrid_t", "char"):
+                want[base] += 1
+    got = dict.fromkeys(_POINTEES, 0)
+    for _, argtypes in capi.FUNCS.values():
+        for a in argtypes:
+            for base, cls in capi.POINTER_TO.items():
+                if a is cls:
+                    got[base] += 1
+    assert got == want and sum(want.values()) > 600 and all(want.values()), (got, want)
+    assert set(capi.POINTER_TO) == set(_POINTEES)
+
+
+# (function, pointee, position of one such parameter), read off the header by hand
+_TYPED = [("ngp_packbits", "float", 0), ("ngp_raygen_aabb", "int64_t", 2), ("ngp_morton3d", "int32_t", 0),
+          ("ngp_bitfield_summary", "uint8_t", 0)]
+_DT = {"float": (torch.float32, torch.int64), "int64_t": (torch.int64, torch.int32),  # pointee: (its dtype, a wrong one)
+       "int32_t": (torch.int32, torch.int64), "uint8_t": (torch.uint8, torch.float32)}
+
+
+@pytest.mark.parametrize("name,pointee,pos", _TYPED)
+@pytest.mark.parametrize("view", ["raw", "checked"])
+def test_typed_pointer_checks_dtype_then_contiguity_then_device(view, name, pointee, pos):
+    """Each raises ctypes.ArgumentError before the C function is entered (no
+    status comes back), and the order of the three checks is pinned: a CPU
+    tensor of the wrong dtype fails on the dtype, a strided one of the right
+    dtype on contiguity, a contiguous one on the device."""
+    fn = getattr(vren.lib() if view == "raw" else vren.kernels(), name)
+    assert capi.FUNCS[name][1][pos] is capi.POINTER_TO[pointee]
+    right, wrong = _DT[pointee]
+    args = [None] * len(capi.FUNCS[name][1])
+    for i, a in enumerate(capi.FUNCS[name][1]):
+        if a in (ctypes.c_int, ctypes.c_int64):
+            args[i] = 0
+        elif a is ctypes.c_float:
+            args[i] = 0.0
+
+    def call(t):
+        a = list(args)
+        a[pos] = t
+        with pytest.raises(ctypes.ArgumentError) as e:
+            fn(*a)
+        assert f"argument {pos + 1}" in str(e.value)
+        return str(e.value)
+
+    msg = call(torch.zeros(8, dtype=wrong))
+    assert str(right) in msg and str(wrong) in msg
+    msg = call(torch.zeros(8, dtype=right)[::2])
+    assert "contiguous" in msg and str(right) not in msg
+    msg = call(torch.zeros(8, dtype=right))
+    assert "CUDA" in msg and "contiguous" not in msg and str(right) not in msg
+
+
+def test_void_pointer_takes_any_dtype_as_far_as_the_device_check():
+    L = vren.lib()
+    pos = 4  # ngp_sample_batch_dev's `const void* gt`
+    assert capi.FUNCS["ngp_sample_batch_dev"][1][pos] is capi.POINTER_TO["void"]
+    for dt in (torch.float16, torch.int32, torch.float64):
+        a = [0, None, 0, 0, torch.zeros(4, dtype=dt), 0, 0, 0, None, None, 0, None, None, 0.0] + [None] * 8
+        with pytest.raises(ctypes.ArgumentError, match="CUDA"):
+            L.ngp_sample_batch_dev(*a)
+        a[pos] = torch.zeros(8, dtype=dt)[::2]
+        with pytest.raises(ctypes.ArgumentError, match="contiguous"):
+            L.ngp_sample_batch_dev(*a)
+
+
+def test_grid_descriptor_passes_as_the_struct_or_by_reference():
+    g = HG.HashGrid(0.5)
+    for L in (vren.lib(), vren.kernels()):
+        assert L.ngp_hash_backward_rep_floats(g.desc, 4, 8) == L.ngp_hash_backward_rep_floats(ctypes.byref(g.desc), 4, 8)
+        assert L.ngp_hash_backward_rep_floats(g.desc, 4, 8) == 8 * 2 * g.offsets[4]
+
+
+def test_checked_view_raises_on_a_status_and_returns_values():
+    K = vren.kernels()
+    with pytest.raises(vren.NGPError, match="ngp_morton3d") as e:
+        K.ngp_morton3d(None, 10, None, None)
+    assert e.value.status == capi.C["NGP_EINVAL"] and "status -1" in str(e.value)
+    assert K.ngp_morton3d(None, 0, None, None) == 0
+    # value-returning functions carry no errcheck
+    assert K.ngp_render_test_capacity(-1, 1) == -1 and K.ngp_render_test_capacity(10, 4) == 40
+    assert K.ngp_probe_count() == capi.C["NGP_P_COUNT"] == vren.lib().ngp_probe_count()
+    assert K.ngp_version() == vren.lib().ngp_version()
+
+
+def test_only_status_returns_are_checked_and_the_raw_view_is_not():
+    K, L = vren.kernels(), vren.lib()
+    assert K is not L and K is vren.kernels() and L is vren.lib()
+    assert capi.INT_VALUES == {"ngp_probe_count"}
+    for name, (restype, argtypes) in capi.FUNCS.items():
+        f = getattr(K, name)
+        assert f.restype is restype and list(f.argtypes) == argtypes, name
+        checked = restype is c_int and name not in capi.INT_VALUES
+        assert (f.errcheck is not None) == checked, name  # ctypes: an unset errcheck reads as None
+        assert getattr(L, name).errcheck is None, name
+    assert L.ngp_morton3d(None, 10, None, None) == -1  # after the checked view was built
