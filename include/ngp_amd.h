@@ -311,6 +311,32 @@ int ngp_render_test_finish_sh(const float* opacity, const float* rays_d, int64_t
 int ngp_probe_sh9_project(const float* rays_d, const float* rgb, const float* opacity, int64_t P, int64_t R,
                           float* rgb_sh, float* trans_sh, void* stream);
 
+/* ------------------------------------------------------ image metrics */
+/* The two numbers the reference's validation step logs per test image
+ * (train.py:68-70, 208-249: torchmetrics PeakSignalNoiseRatio and
+ * StructuralSimilarityIndexMeasure, data_range 1), in one pass over the frame.
+ * pred, gt (h*w,3) f32, row-major pixels with interleaved channels (what
+ * render() returns and dataset.rays[i] holds); clamp01 != 0 clamps pred (never
+ * gt) to [0,1] on load.  out (2) f32: out[0] = the MSE over all 3*h*w elements,
+ * out[1] = the SSIM = the mean over 3 channels x (h-10)*(w-10) windows of
+ *   (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx2 + sy2 + C2)),
+ * C1 = 1e-4, C2 = 9e-4, the moments weighted by the separable 11x11 Gaussian
+ * window (sigma 1.5, normalised to sum 1): mx = E[x], sx2 = E[x^2] - mx^2,
+ * sxy = E[xy] - mx my.  Only whole windows count (torchmetrics pads by
+ * reflection and crops the padded border away again: the same mean).
+ * ssim_map (nullable): (3, h-10, w-10) f32, channel-major, one index per window.
+ * Weights, products, window sums, the index and every reduction are fp64; each
+ * stored value is rounded to fp32 once.  One workgroup per tile of windows
+ * leaves its two sums in its own slot of ws, a second launch adds the slots in
+ * index order: no atomics, the same bits from call to call.  ws:
+ * ngp_image_metrics_ws_bytes(h, w) bytes (0 for sizes ngp_image_metrics
+ * refuses), 8-byte aligned, contents irrelevant before and after.
+ * NGP_EINVAL: a null pred / gt / ws / out, a misaligned ws, h < 11 or w < 11;
+ * NGP_ERANGE: 3*h*w >= 2^31. */
+size_t ngp_image_metrics_ws_bytes(int h, int w);
+int ngp_image_metrics(const float* pred, const float* gt, int h, int w, int clamp01, void* ws, float* out,
+                      float* ssim_map, void* stream);
+
 /* --------------------------------------------- hash grid + fused MLPs */
 /* Level table of tcnn's Grid/Hash encoding as configured at
  * models/networks.py:33-49 (host function; fp32 arithmetic like tcnn).

@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
-"""Train on a real scene and report test PSNR -- the reference's train.py
-flow (NeRFSystem: mark_invisible_cells, 8192-ray batches, occupancy updates
-every 16 steps, Adam + cosine lr, test renders at the end) on the native
-trainer.  Usage:
+"""Train on a real scene and report test PSNR and SSIM -- the reference's
+train.py flow (NeRFSystem: mark_invisible_cells, 8192-ray batches, occupancy
+updates every 16 steps, Adam + cosine lr, test renders at the end) on the
+native trainer.  Usage:
   python scripts/train_scene.py --dataset nsvf --root /data/Synthetic_NeRF/Lego --steps 30000
-Prints one JSON line: rays/s of the training loop and the mean test PSNR
-(render(test_time=True): device-resident loop, black background -> the
-reference evaluates synthetic scenes on white GT, so bg=1 like train.py's
-validation for esf == 0)."""
+Prints one JSON line: rays/s of the training loop and the mean test PSNR and
+SSIM over the test images (metrics.ImageMetrics: the reference's test/psnr and
+test/ssim, train.py:208-249; render(test_time=True): device-resident loop,
+black background -> the reference evaluates synthetic scenes on white GT, so
+bg=1 like train.py's validation for esf == 0)."""
 import argparse
 import json
-import math
 import os
 import sys
 import time
@@ -76,15 +76,16 @@ def main(argv=None):
     t_train = time.perf_counter() - t0
     n = len(test.poses) if a.test_views <= 0 else min(a.test_views, len(test.poses))
     tdirs = test.directions.to(dev)
-    psnrs = []
+    from metrics import ImageMetrics
+    im = ImageMetrics(test.img_wh, max(1, n), dev)  # per-frame MSE and SSIM stay on the device: one sync after the loop
     for i in range(n):
         P = test.poses[i].to(dev)
         d = (tdirs @ P[:, :3].t()).contiguous()
         o = P[:, 3].expand_as(d).contiguous()
         out = tr.render(o, d, bg=1.0 if tr.esf == 0 else 0.0, output_radiance=a.use_raw_HDR)
-        pred = out["rgb"] if a.use_raw_HDR else out["rgb"].clamp(0, 1)  # (radiance is not clamped to [0,1])
-        mse = torch.mean((pred - test.rays[i].to(dev)[..., :3].float()) ** 2).item()
-        psnrs.append(-10 * math.log10(max(mse, 1e-12)))
+        # sigmoid models are scored clamped to [0,1]; radiance is not clamped
+        im.update(out["rgb"], test.rays[i].to(dev)[..., :3].float().contiguous(), clamp=not a.use_raw_HDR)
+    scores = im.compute()
     if a.ckpt:
         ck = {"params": tr.full_params().detach().cpu()}
         if tr.pose_refiner is not None:
@@ -95,7 +96,7 @@ def main(argv=None):
            "use_raw_HDR": bool(a.use_raw_HDR), "optimize_ext": bool(a.optimize_ext),
            "guard_hits": int(vren.lib().ngp_guard_hits()),
            "train_rays_per_s": round(a.steps * a.batch / t_train, 1),
-           "test_psnr": round(sum(psnrs) / max(1, len(psnrs)), 3), "test_views": n}
+           "test_psnr": round(scores["mean_psnr"], 3), "test_ssim": round(scores["mean_ssim"], 4), "test_views": n}
     print(json.dumps(res))
     return res
 
