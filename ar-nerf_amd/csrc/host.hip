@@ -49,6 +49,18 @@ __global__ void trace_marker_kernel(int tag) {
     if (tag < 0) __builtin_trap();  // (never: keeps the argument live)
 }
 
+// the raw generator, one (counter, key) row per lane (ngp_philox4x32): the
+// philox4x32 of common.h that every drawing kernel calls
+__global__ void __launch_bounds__(256) philox_kernel(const uint32_t* __restrict__ counters,
+                                                     const uint32_t* __restrict__ keys, int64_t n,
+                                                     uint32_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t* c = counters + 4 * i;
+    const uint4 r = ngp::philox4x32(make_uint4(c[0], c[1], c[2], c[3]), make_uint2(keys[2 * i], keys[2 * i + 1]));
+    out[4 * i] = r.x; out[4 * i + 1] = r.y; out[4 * i + 2] = r.z; out[4 * i + 3] = r.w;
+}
+
 extern "C" {
 
 const char* ngp_version(void) { return "ngp_amd 0.2 gfx950"; }
@@ -96,6 +108,14 @@ int ngp_guard_reset(void) {
 int ngp_trace_marker(int tag, void* stream) {
     NGP_CHECK_ARG(tag >= 0);
     trace_marker_kernel<<<1, 64, 0, as_stream(stream)>>>(tag);
+    return ngp_launch_status();
+}
+
+int ngp_philox4x32(const uint32_t* counters, const uint32_t* keys, int64_t n, uint32_t* out, void* stream) {
+    NGP_CHECK_ARG(n >= 0);
+    if (n == 0) return NGP_OK;
+    NGP_CHECK_ARG(counters && keys && out && (n + 255) / 256 <= 0x7fffffffll);
+    philox_kernel<<<(unsigned)((n + 255) / 256), 256, 0, as_stream(stream)>>>(counters, keys, n, out);
     return ngp_launch_status();
 }
 

@@ -50,6 +50,15 @@ THROTTLE_EVERY, THROTTLE_DEPTH = 32, 4  # host run-ahead bound: <= 160 steps enq
 COARSE_REP, COARSE_REP_LEVELS = 8, 4  # gradient replicas of the coarsest atomic levels
 
 
+def rng_keys(seed):
+    """The trainer's three Philox keys (64 bits each) from its seed:
+    (sample_seed: the batch draw, ngp_sample_batch; its random-background key,
+    ngp_random_bg; occ_seed: the occupancy draws, ngp_occupancy_samples*).
+    Pairwise different for every seed: they differ by the xor constants."""
+    base = (1000003 * (seed + 1)) & 0xFFFFFFFFFFFFFFFF
+    return base, base ^ 0x6267, (base ^ 0x5DEECE66D) & 0xFFFFFFFFFFFFFFFF
+
+
 class NGPTrainer:
     def __init__(self, scale=0.5, batch_size=8192, lr=1e-2, num_epochs=30, steps_per_epoch=1000, loss="raw",
                  lambda_opacity=1e-3, lambda_depth=0.0, random_bg=False, exp_step_factor=None, grid_size=128,
@@ -301,10 +310,9 @@ class NGPTrainer:
         self.gen.manual_seed(1000 + seed + self.rank)
         # ngp_sample_batch key: one seed for all ranks, rank r draws rays [r*R, (r+1)*R) of the global
         # batch (independent uniform draws per ray, as the reference's per-rank DataLoaders)
-        self.sample_seed = (1000003 * (seed + 1)) & 0xFFFFFFFFFFFFFFFF
         # occupancy draws: rank-independent (every rank draws the same cells and
         # jitter; each evaluates its shard), so any world size builds one grid
-        self.occ_seed = ((1000003 * (seed + 1)) ^ 0x5DEECE66D) & 0xFFFFFFFFFFFFFFFF
+        self.sample_seed, self.bg_seed, self.occ_seed = rng_keys(seed)
         self.occ_gen = torch.Generator(device=dev)
         self.occ_gen.manual_seed(2000 + seed)
         # device step counters: [0] Adam steps taken, [1] batches drawn (RNG
@@ -1156,7 +1164,7 @@ class NGPTrainer:
         bg = self.bg
         if self.random_bg:  # rendering.py:287-288, one colour per batch, drawn on device (graph-safe)
             bg = self._bg_rand
-            L.ngp_random_bg(self.sample_seed ^ 0x6267, self.dctr[1:], 0, bg, s)
+            L.ngp_random_bg(self.bg_seed, self.dctr[1:], 0, bg, s)
         self._ev("composite_loss", 0)
         self._ev("composite", 0)
         L.ngp_composite_loss(self.sigmas, self.rgbs, self.deltas, self.ts, self.rays_a, R, rgb_gt, bg, self.loss_type,

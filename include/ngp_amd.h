@@ -81,6 +81,11 @@ int ngp_probe_count(void);
 /* Launches an empty kernel named trace_marker_kernel (tag >= 0) on `stream`:
  * brackets a window of a rocprofv3 dispatch trace (scripts/roofline_check.py). */
 int ngp_trace_marker(int tag, void* stream);
+/* The raw generator (tests): out row i = Philox-4x32-10 (Salmon et al.,
+ * SC'11) of counter row i under key row i -- the device function every draw
+ * below calls (batch, background, occupancy cells).  counters (n,4), keys
+ * (n,2), out (n,4) u32. */
+int ngp_philox4x32(const uint32_t* counters, const uint32_t* keys, int64_t n, uint32_t* out, void* stream);
 
 /* ---------------------------------------------------------------- rays */
 /* Replaces vren.ray_aabb_intersect (binding.cpp:9-20 -> intersection.cu:59-100).

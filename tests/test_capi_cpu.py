@@ -91,6 +91,20 @@ def test_new_entry_points_reject_bad_arguments_without_launching():
     assert L.ngp_density_input_grad(None, 5, C.byref(g.desc), None, None, None, None, None) == -1
 
 
+def test_raw_generator_entry_point_checks_arguments_without_launching():
+    """ngp_philox4x32: a negative count or a null pointer is NGP_EINVAL (-1)
+    before any launch, no rows are a no-op."""
+    import ctypes as C
+    L = HG._lib()
+    p = C.c_void_p(256)  # never dereferenced: every call below fails its checks first (or has nothing to do)
+    assert L.ngp_philox4x32(p, p, -1, p, None) == -1
+    assert L.ngp_philox4x32(None, p, 4, p, None) == -1
+    assert L.ngp_philox4x32(p, None, 4, p, None) == -1
+    assert L.ngp_philox4x32(p, p, 4, None, None) == -1
+    assert L.ngp_philox4x32(None, None, 0, None, None) == 0 and L.ngp_philox4x32(p, p, 0, p, None) == 0
+    assert capi.FUNCS["ngp_philox4x32"] == (c_int, [_u32p, _u32p, c_int64, _u32p, _vp])
+
+
 def test_gradient_replica_entry_points_check_arguments_without_launching():
     """ngp_hash_backward_levels_rep / ngp_hash_backward_rep_floats /
     ngp_adam_step_dev_rep: sizes and
