@@ -66,43 +66,76 @@ __device__ __forceinline__ void fetch_pair(const uint32_t* __restrict__ tl, uint
     v1 = i0 < i1 ? vhi : vlo;
 }
 
-// Hash-encode level l of one sample: the two features (fp32 accumulation,
-// rounded once to fp16 by the caller).
-__device__ __forceinline__ void encode_level(const float in[3], int l, const LevelLds& lv,
-                                             const uint32_t* __restrict__ table, float& a0, float& a1) {
-    const float sc = lv.scale[l];
-    const uint32_t res = lv.res[l], size = lv.size[l], off = lv.off[l];
-    const bool dense = (lv.dense >> l) & 1u, pow2 = (lv.pow2 >> l) & 1u;
+// ------------------------------------------------------ one level's encoding
+// One level's parameters as wave-uniform (scalar) values, so the per-level
+// index variant is chosen by scalar branches, not computed for every lane.
+struct LevelU {
+    float sc;
+    uint32_t res, res2, size, off;
+    bool dense, pow2;
+};
+__device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ LevelU level_u(const LevelLds& lv, int l) {
+    LevelU u;
+    u.sc = __uint_as_float(rfl(__float_as_uint(lv.scale[l])));
+    u.res = rfl(lv.res[l]);
+    u.res2 = u.res * u.res;
+    u.size = rfl(lv.size[l]);
+    u.off = rfl(lv.off[l]);
+    u.dense = (rfl(lv.dense) >> l) & 1u;
+    u.pow2 = (rfl(lv.pow2) >> l) & 1u;
+    return u;
+}
+// the same level as per-lane values (l differs between the lanes of a wave)
+__device__ __forceinline__ LevelU level_lane(const LevelLds& lv, int l) {
+    return LevelU{lv.scale[l], lv.res[l], lv.res[l] * lv.res[l], lv.size[l], lv.off[l], (bool)((lv.dense >> l) & 1u),
+                  (bool)((lv.pow2 >> l) & 1u)};
+}
+
+// grid.h's cell and corner index of a level held as LevelU
+__device__ __forceinline__ void level_cell(const float in[3], const LevelU& u, uint32_t pg[3], float pos[3]) {
+    level_cell(u.sc, in, pg, pos);
+}
+__device__ __forceinline__ uint32_t corner_index(uint32_t px, uint32_t py, uint32_t pz, const LevelU& u) {
+    return reduce_index(raw_index(px, py, pz, u.res, u.res2, u.dense), u.size, u.dense, u.pow2);
+}
+
+// The indices i0 (corner x) and i1 (corner x + 1) of y/z pair yz of cell pg.
+__device__ __forceinline__ void pair_index(const uint32_t pg[3], int yz, const LevelU& u, uint32_t& i0, uint32_t& i1) {
+    const uint32_t qy = pg[1] + (yz & 1), qz = pg[2] + (yz >> 1);
+    i0 = corner_index(pg[0], qy, qz, u);
+    i1 = corner_index(pg[0] + 1u, qy, qz, u);
+}
+
+// The level's eight table entries of cell pg, as four x-adjacent pairs
+// (v[2 yz], v[2 yz + 1]: corners (0, y, z) and (1, y, z)): every index first,
+// then the four fetch_pair loads.
+// (level sizes are multiples of 4 and offsets of 8 entries: the aligned
+// groups stay inside the level)
+__device__ __forceinline__ void gather_cell(const uint32_t pg[3], const LevelU& u, const uint32_t* __restrict__ table,
+                                            uint32_t v[8]) {
+    uint32_t i0[4], i1[4];
+#pragma unroll
+    for (int yz = 0; yz < 4; ++yz) pair_index(pg, yz, u, i0[yz], i1[yz]);
+    const uint32_t* tl = table + u.off;
+#pragma unroll
+    for (int yz = 0; yz < 4; ++yz) fetch_pair(tl, i0[yz], i1[yz], u.dense || !u.pow2, v[2 * yz], v[2 * yz + 1]);
+}
+
+// One level's encoding in two halves, so a caller can issue the gathers of
+// several levels before it consumes any: corner weights + the level's loads,
+// then the fp32 corner sum (fmaf over the corners in tcnn's order; the caller
+// rounds once to fp16)
+__device__ __forceinline__ void gather_level_u(const float in[3], const LevelU& u, const uint32_t* __restrict__ table,
+                                               float w[8], uint32_t v[8]) {
     float pos[3];
     uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = fmaf(sc, in[d], 0.5f);
-        const float fl = floorf(p);
-        pg[d] = (uint32_t)(int)fl;
-        pos[d] = p - fl;
-    }
-    uint32_t v[8];
-    float w[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        float wt = 1.0f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) wt *= (c & (1 << d)) ? pos[d] : 1 - pos[d];
-        w[c] = wt;
-    }
-    // x-adjacent corner pairs: one 8-byte load when the two entries are
-    // neighbours (always on dense levels; on hashed levels when px is
-    // even, the x term of the hash being px*1), else two 4-byte loads.
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) {
-        const uint32_t qy = pg[1] + (yz & 1), qz = pg[2] + (yz >> 1);
-        const uint32_t i0 = corner_index(pg[0], qy, qz, res, size, dense, pow2);
-        const uint32_t i1 = corner_index(pg[0] + 1, qy, qz, res, size, dense, pow2);
-        // (level sizes are multiples of 4 and offsets of 8 entries: the
-        // aligned groups stay inside the level)
-        fetch_pair(table + off, i0, i1, dense || !pow2, v[2 * yz], v[2 * yz + 1]);
-    }
+    level_cell(in, u, pg, pos);
+    corner_weights(pos, w);
+    gather_cell(pg, u, table, v);
+}
+
+__device__ __forceinline__ void sum_level(const float w[8], const uint32_t v[8], float& a0, float& a1) {
     a0 = 0.f;
     a1 = 0.f;
 #pragma unroll
@@ -114,13 +147,58 @@ __device__ __forceinline__ void encode_level(const float in[3], int l, const Lev
     }
 }
 
+__device__ __forceinline__ uint32_t pack_h2(float a, float b) {
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)b) << 16);
+}
+
+// gather_level_u in two halves that keep fewer registers live across the
+// loads' latency: the loads alone (indices from the cell corner), then -- once
+// they have returned -- the corner weights recomputed from the position and
+// the fp32 corner sum
+__device__ __forceinline__ void gather_level_loads(const float in[3], const LevelU& u,
+                                                   const uint32_t* __restrict__ table, uint32_t v[8]) {
+    float pos[3];
+    uint32_t pg[3];
+    level_cell(in, u, pg, pos);
+    gather_cell(pg, u, table, v);
+}
+__device__ __forceinline__ uint32_t level_sum_h2(const float in[3], const LevelU& u, const uint32_t v[8]) {
+    float pos[3], w[8];
+    uint32_t pg[3];
+    level_cell(in, u, pg, pos);
+    corner_weights(pos, w);
+    float a0, a1;
+    sum_level(w, v, a0, a1);
+    return pack_h2(a0, a1);
+}
+
+// Hash-encode one level of one sample: the two features (fp32 accumulation,
+// rounded once to fp16 by the caller).
+__device__ __forceinline__ void encode_level(const float in[3], const LevelU& u, const uint32_t* __restrict__ table,
+                                             float& a0, float& a1) {
+    float pos[3], w[8];
+    uint32_t pg[3], v[8];
+    level_cell(in, u, pg, pos);
+    corner_weights(pos, w);
+    // (each pair's load right after its indices, not gather_cell's indices-first order: with
+    // that, field_fwd_kernel<false> needs 123 VGPRs instead of 127 and gains an occupancy
+    // step, which resizes its persistent grid)
+#pragma unroll
+    for (int yz = 0; yz < 4; ++yz) {
+        uint32_t i0, i1;
+        pair_index(pg, yz, u, i0, i1);
+        fetch_pair(table + u.off, i0, i1, u.dense || !u.pow2, v[2 * yz], v[2 * yz + 1]);
+    }
+    sum_level(w, v, a0, a1);
+}
+
 // Hash-encode levels 4g..4g+3 of one sample -> 8 fp16 values (enc[8g..8g+7]).
 __device__ __forceinline__ h8 encode4(const float in[3], int g, const LevelLds& lv, const uint32_t* __restrict__ table) {
     h8 e;
 #pragma unroll
     for (int jl = 0; jl < 4; ++jl) {
         float a0, a1;
-        encode_level(in, 4 * g + jl, lv, table, a0, a1);
+        encode_level(in, level_lane(lv, 4 * g + jl), table, a0, a1);
         e[2 * jl] = (_Float16)a0;
         e[2 * jl + 1] = (_Float16)a1;
     }
@@ -189,159 +267,6 @@ __global__ void __launch_bounds__(256) field_fwd_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------ hash encode alone
-// One level's parameters as wave-uniform (scalar) values, so the per-level
-// index variant is chosen by scalar branches, not computed for every lane.
-struct LevelU {
-    float sc;
-    uint32_t res, res2, size, off;
-    bool dense, pow2;
-};
-__device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ LevelU level_u(const LevelLds& lv, int l) {
-    LevelU u;
-    u.sc = __uint_as_float(rfl(__float_as_uint(lv.scale[l])));
-    u.res = rfl(lv.res[l]);
-    u.res2 = u.res * u.res;
-    u.size = rfl(lv.size[l]);
-    u.off = rfl(lv.off[l]);
-    u.dense = (rfl(lv.dense) >> l) & 1u;
-    u.pow2 = (rfl(lv.pow2) >> l) & 1u;
-    return u;
-}
-
-// encode_level with the same values (tcnn grid_index, fmaf corner order), but
-// the index reduction specialised per level: hashed levels have a power-of-two
-// size (mask); on dense levels the corner index is below 2 * size (corner
-// coordinates <= res, size >= res^3), so `% size` is one conditional
-// subtract; the generic modulo remains for any other table.
-__device__ __forceinline__ uint32_t reduce_idx(uint32_t idx, const LevelU& u) {
-    if (u.pow2) return idx & (u.size - 1u);
-    if (u.dense) {
-        // below 2 * size for coordinates in [0, res]; inputs outside the grid's box
-        // (coordinates past it) take the full modulo, as tcnn's grid_index does
-        idx = idx >= u.size ? idx - u.size : idx;
-        return __builtin_expect(idx >= u.size, 0) ? idx % u.size : idx;
-    }
-    return idx % u.size;
-}
-
-// encode_level_u in two halves, so a caller can issue the gathers of several
-// levels before it consumes any: corner weights + the level's loads, then the
-// fp32 corner sum (the same fmaf order)
-__device__ __forceinline__ void gather_level_u(const float in[3], const LevelU& u, const uint32_t* __restrict__ table,
-                                               float w[8], uint32_t v[8]) {
-    float pos[3];
-    uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = fmaf(u.sc, in[d], 0.5f);
-        const float fl = floorf(p);
-        pg[d] = (uint32_t)(int)fl;
-        pos[d] = p - fl;
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        float wt = 1.0f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) wt *= (c & (1 << d)) ? pos[d] : 1 - pos[d];
-        w[c] = wt;
-    }
-    uint32_t i0[4], i1[4];
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) {
-        const uint32_t qy = pg[1] + (yz & 1), qz = pg[2] + (yz >> 1);
-        uint32_t r0, r1;
-        if (u.dense) {
-            r0 = pg[0] + qy * u.res + qz * u.res2;
-            r1 = r0 + 1u;
-        } else {
-            const uint32_t h = (qy * 2654435761u) ^ (qz * 805459861u);
-            r0 = (pg[0] * 1u) ^ h;
-            r1 = ((pg[0] + 1u) * 1u) ^ h;
-        }
-        i0[yz] = reduce_idx(r0, u);
-        i1[yz] = reduce_idx(r1, u);
-    }
-    const uint32_t* tl = table + u.off;
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) fetch_pair(tl, i0[yz], i1[yz], u.dense || !u.pow2, v[2 * yz], v[2 * yz + 1]);
-}
-
-__device__ __forceinline__ void sum_level(const float w[8], const uint32_t v[8], float& a0, float& a1) {
-    a0 = 0.f;
-    a1 = 0.f;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        const _Float16 f0 = __builtin_bit_cast(_Float16, (uint16_t)(v[c] & 0xffffu));
-        const _Float16 f1 = __builtin_bit_cast(_Float16, (uint16_t)(v[c] >> 16));
-        a0 = fmaf(w[c], (float)f0, a0);
-        a1 = fmaf(w[c], (float)f1, a1);
-    }
-}
-
-// gather_level_u in two halves that keep fewer registers live across the
-// loads' latency: the loads alone (indices from the cell corner), then -- once
-// they have returned -- the corner weights recomputed from the position and
-// the fp32 corner sum (the same values, the same fmaf order)
-__device__ __forceinline__ void level_cell(const float in[3], const LevelU& u, uint32_t pg[3], float pos[3]) {
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = fmaf(u.sc, in[d], 0.5f);
-        const float fl = floorf(p);
-        pg[d] = (uint32_t)(int)fl;
-        pos[d] = p - fl;
-    }
-}
-__device__ __forceinline__ void gather_level_loads(const float in[3], const LevelU& u,
-                                                   const uint32_t* __restrict__ table, uint32_t v[8]) {
-    float pos[3];
-    uint32_t pg[3];
-    level_cell(in, u, pg, pos);
-    uint32_t i0[4], i1[4];
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) {
-        const uint32_t qy = pg[1] + (yz & 1), qz = pg[2] + (yz >> 1);
-        uint32_t r0, r1;
-        if (u.dense) {
-            r0 = pg[0] + qy * u.res + qz * u.res2;
-            r1 = r0 + 1u;
-        } else {
-            const uint32_t h = (qy * 2654435761u) ^ (qz * 805459861u);
-            r0 = (pg[0] * 1u) ^ h;
-            r1 = ((pg[0] + 1u) * 1u) ^ h;
-        }
-        i0[yz] = reduce_idx(r0, u);
-        i1[yz] = reduce_idx(r1, u);
-    }
-    const uint32_t* tl = table + u.off;
-#pragma unroll
-    for (int yz = 0; yz < 4; ++yz) fetch_pair(tl, i0[yz], i1[yz], u.dense || !u.pow2, v[2 * yz], v[2 * yz + 1]);
-}
-__device__ __forceinline__ uint32_t level_sum_h2(const float in[3], const LevelU& u, const uint32_t v[8]) {
-    float pos[3];
-    uint32_t pg[3];
-    level_cell(in, u, pg, pos);
-    float w[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        float wt = 1.0f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) wt *= (c & (1 << d)) ? pos[d] : 1 - pos[d];
-        w[c] = wt;
-    }
-    float a0, a1;
-    sum_level(w, v, a0, a1);
-    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)a0) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)a1) << 16);
-}
-
-__device__ __forceinline__ void encode_level_u(const float in[3], const LevelU& u, const uint32_t* __restrict__ table,
-                                               float& a0, float& a1) {
-    float w[8];
-    uint32_t v[8];
-    gather_level_u(in, u, table, w, v);
-    sum_level(w, v, a0, a1);
-}
-
 // Multires hash encoding alone (the gathers of field_fwd_kernel, same
 // arithmetic, bit-identical values), written pair-major:
 //   enc_pm[p][i][0..3] = enc[i][4p .. 4p+3]  (levels 2p, 2p+1; p = 0..7).
@@ -422,16 +347,29 @@ __device__ __forceinline__ void transpose_rows4(uint32_t E[16]) {
     }
 }
 
-__device__ __forceinline__ uint32_t pack_h2(float a, float b) {
-    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)a) | ((uint32_t)__builtin_bit_cast(uint16_t, (_Float16)b) << 16);
-}
-
 // 8 waves per block; 2 levels per gather round (4: the loads of 4 levels in flight need > 128
 // VGPRs and spill, -3 %)
 constexpr int FEM2_WAVES = 8, FEM_LPR = 2;
 constexpr int PRE_LEVELS = 8;  // coarse levels round 1 may find pre-encoded (encode_coarse_first_kernel)
 static_assert(PRE_LEVELS % FEM_LPR == 0 && PRE_LEVELS % 2 == 0, "pre-encoded levels: whole rounds and pairs");
 static_assert(L % FEM_LPR == 0, "levels per round");
+// The gather rounds [r0, L / FEM_LPR) of one sample's encoding, FEM_LPR levels each, not
+// unrolled (an unrolled chain hoists every round's loads: 256 VGPRs); each round shifts its
+// levels into the top of E (fp16x2 per level), so after the last round E[l] holds level l
+// (levels below FEM_LPR * r0: whatever the caller put at the top of E).
+__device__ __forceinline__ void encode_rounds(const float in[3], const LevelLds& lv, const uint32_t* __restrict__ table,
+                                              int r0, uint32_t E[16]) {
+#pragma unroll 1
+    for (int r = r0; r < L / FEM_LPR; ++r) {
+        uint32_t v[FEM_LPR][8];
+#pragma unroll
+        for (int q = 0; q < FEM_LPR; ++q) gather_level_loads(in, level_u(lv, FEM_LPR * r + q), table, v[q]);
+#pragma unroll
+        for (int q = 0; q < 16 - FEM_LPR; ++q) E[q] = E[q + FEM_LPR];
+#pragma unroll
+        for (int q = 0; q < FEM_LPR; ++q) E[16 - FEM_LPR + q] = level_sum_h2(in, level_u(lv, FEM_LPR * r + q), v[q]);
+    }
+}
 template <bool COLOR>
 __global__ void __launch_bounds__(64 * FEM2_WAVES, FEM2_WAVES / 2) field_encode_mlp_reg_kernel(
     const float* __restrict__ xyzs, const float* __restrict__ dirs, int64_t n, const int64_t* __restrict__ n_dev,
@@ -474,19 +412,7 @@ __global__ void __launch_bounds__(64 * FEM2_WAVES, FEM2_WAVES / 2) field_encode_
         }
         first = false;
         uint32_t E[16];  // level l's two features, fp16x2
-        // rounds of FEM_LPR levels, not unrolled (an unrolled chain hoists every round's
-        // loads: 256 VGPRs); each round shifts its levels into the top of E, so after the
-        // last round E[l] holds level l
-#pragma unroll 1
-        for (int r = 0; r < L / FEM_LPR; ++r) {
-            uint32_t v[FEM_LPR][8];
-#pragma unroll
-            for (int q = 0; q < FEM_LPR; ++q) gather_level_loads(in, level_u(lv, FEM_LPR * r + q), table, v[q]);
-#pragma unroll
-            for (int q = 0; q < 16 - FEM_LPR; ++q) E[q] = E[q + FEM_LPR];
-#pragma unroll
-            for (int q = 0; q < FEM_LPR; ++q) E[16 - FEM_LPR + q] = level_sum_h2(in, level_u(lv, FEM_LPR * r + q), v[q]);
-        }
+        encode_rounds(in, lv, table, 0, E);
         if (valid && enc_pm) {
 #pragma unroll
             for (int pr = 0; pr < 8; ++pr)
@@ -557,16 +483,7 @@ __device__ __forceinline__ float encode_mlp_chunk(const float* __restrict__ xyzs
             E[16 - PRE_LEVELS + 2 * pr + 1] = q.y;
         }
     }
-#pragma unroll 1
-    for (int rr = pre / FEM_LPR; rr < L / FEM_LPR; ++rr) {
-        uint32_t v[FEM_LPR][8];
-#pragma unroll
-        for (int q = 0; q < FEM_LPR; ++q) gather_level_loads(in, level_u(lv, FEM_LPR * rr + q), table, v[q]);
-#pragma unroll
-        for (int q = 0; q < 16 - FEM_LPR; ++q) E[q] = E[q + FEM_LPR];
-#pragma unroll
-        for (int q = 0; q < FEM_LPR; ++q) E[16 - FEM_LPR + q] = level_sum_h2(in, level_u(lv, FEM_LPR * rr + q), v[q]);
-    }
+    encode_rounds(in, lv, table, pre / FEM_LPR, E);
     if (valid && enc_pm) {
 #pragma unroll
         for (int pr = 0; pr < 8; ++pr)
@@ -743,13 +660,7 @@ __device__ __forceinline__ void coarse_level_runs(const float in[3], bool valid,
     const bool dense = (lv.dense >> l) & 1u, pow2 = (lv.pow2 >> l) & 1u;
     float pos[3];
     uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = fmaf(sc, in[d], 0.5f);
-        const float fl = floorf(p);
-        pg[d] = (uint32_t)(int)fl;
-        pos[d] = p - fl;
-    }
+    level_cell(sc, in, pg, pos);
     // corner c = cx | (cy<<1) | (cz<<2); weight product in tcnn's d order.
     // The four y/z corners are independent: their shuffles are issued
     // together (one LDS round trip per scan step, not four).

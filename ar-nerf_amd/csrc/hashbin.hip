@@ -125,13 +125,7 @@ __device__ __forceinline__ Rec make_rec(const float in[3], float2 gd, int cy, in
     const bool dense = (lv.dense >> l) & 1u, pow2 = (lv.pow2 >> l) & 1u;
     float pos[3];
     uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = fmaf(sc, in[d], 0.5f);
-        const float fl = floorf(p);
-        pg[d] = (uint32_t)(int)fl;
-        pos[d] = p - fl;
-    }
+    level_cell(sc, in, pg, pos);
     const float wyz = (cy ? pos[1] : 1 - pos[1]) * (cz ? pos[2] : 1 - pos[2]);
     Rec r;
     r.fx = pos[0];

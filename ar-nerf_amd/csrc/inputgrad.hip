@@ -86,13 +86,7 @@ __device__ __forceinline__ void level_pos_grad(const float in[3], int l, const L
     const bool dense = (lv.dense >> l) & 1u, pow2 = (lv.pow2 >> l) & 1u;
     float pos[3];
     uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = fmaf(sc, in[d], 0.5f);
-        const float fl = floorf(p);
-        pg[d] = (uint32_t)(int)fl;
-        pos[d] = p - fl;
-    }
+    level_cell(sc, in, pg, pos);
     uint32_t v[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c)
@@ -103,15 +97,7 @@ __device__ __forceinline__ void level_pos_grad(const float in[3], int l, const L
     for (int c = 0; c < 8; ++c) {
         const float t0 = (float)__builtin_bit_cast(_Float16, (uint16_t)(v[c] & 0xffffu));
         const float t1 = (float)__builtin_bit_cast(_Float16, (uint16_t)(v[c] >> 16));
-        const float val = d0 * t0 + d1 * t1;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            float dw = (c >> d) & 1 ? 1.0f : -1.0f;  // d/dpos_d of the corner weight
-#pragma unroll
-            for (int d2 = 0; d2 < 3; ++d2)
-                if (d2 != d) dw *= (c >> d2) & 1 ? pos[d2] : 1 - pos[d2];
-            acc[d] = fmaf(dw, val, acc[d]);
-        }
+        corner_pos_grad(pos, c, d0 * t0 + d1 * t1, acc);
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d) gx[d] = fmaf(sc, acc[d], gx[d]);

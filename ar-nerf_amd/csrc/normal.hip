@@ -38,22 +38,14 @@ __global__ void __launch_bounds__(256) density_input_grad_kernel(const float* __
     for (int l = 0; l < L; ++l) {
         float pos[3];
         uint32_t pg[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float p = fmaf(lv.scale[l], in[d], 0.5f);
-            const float fl = floorf(p);
-            pg[d] = (uint32_t)(int)fl;
-            pos[d] = p - fl;
-        }
+        level_cell(lv.scale[l], in, pg, pos);
         const bool dense = (lv.dense >> l) & 1u, pow2 = (lv.pow2 >> l) & 1u;
         float a0 = 0.f, a1 = 0.f;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            float w = 1.0f;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) w *= (c >> d) & 1 ? pos[d] : 1 - pos[d];
             const uint32_t e = lv.off[l] + corner_index(pg[0] + (c & 1), pg[1] + ((c >> 1) & 1),
                                                         pg[2] + ((c >> 2) & 1), lv.res[l], lv.size[l], dense, pow2);
+            const float w = corner_weight(pos, c);
             a0 = fmaf(w, (float)table[2 * (size_t)e], a0);
             a1 = fmaf(w, (float)table[2 * (size_t)e + 1], a1);
         }
@@ -89,13 +81,7 @@ __global__ void __launch_bounds__(256) density_input_grad_kernel(const float* __
     for (int l = 0; l < L; ++l) {
         float pos[3];
         uint32_t pg[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            const float p = fmaf(lv.scale[l], in[d], 0.5f);
-            const float fl = floorf(p);
-            pg[d] = (uint32_t)(int)fl;
-            pos[d] = p - fl;
-        }
+        level_cell(lv.scale[l], in, pg, pos);
         const bool dense = (lv.dense >> l) & 1u, pow2 = (lv.pow2 >> l) & 1u;
         float acc[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -103,14 +89,7 @@ __global__ void __launch_bounds__(256) density_input_grad_kernel(const float* __
             const uint32_t e = lv.off[l] + corner_index(pg[0] + (c & 1), pg[1] + ((c >> 1) & 1),
                                                         pg[2] + ((c >> 2) & 1), lv.res[l], lv.size[l], dense, pow2);
             const float v = genc[2 * l] * (float)table[2 * (size_t)e] + genc[2 * l + 1] * (float)table[2 * (size_t)e + 1];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                float dw = (c >> d) & 1 ? 1.0f : -1.0f;  // d/dpos_d of the corner weight
-#pragma unroll
-                for (int d2 = 0; d2 < 3; ++d2)
-                    if (d2 != d) dw *= (c >> d2) & 1 ? pos[d2] : 1 - pos[d2];
-                acc[d] = fmaf(dw, v, acc[d]);
-            }
+            corner_pos_grad(pos, c, v, acc);
         }
 #pragma unroll
         for (int d = 0; d < 3; ++d) gx[d] = fmaf(lv.scale[l], acc[d], gx[d]);

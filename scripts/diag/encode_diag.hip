@@ -96,25 +96,12 @@ __device__ __forceinline__ void gather_level_at(const float in[3], const LevelU&
                                                 uint32_t v[8]) {
     float pos[3];
     uint32_t pg[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float p = fmaf(u.sc, in[d], 0.5f);
-        const float fl = floorf(p);
-        pg[d] = (uint32_t)(int)fl;
-        pos[d] = p - fl;
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        float wt = 1.0f;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) wt *= (c & (1 << d)) ? pos[d] : 1 - pos[d];
-        w[c] = wt;
-    }
+    level_cell(in, u, pg, pos);
+    corner_weights(pos, w);
 #pragma unroll
     for (int yz = 0; yz < 4; ++yz) {
-        const uint32_t qy = pg[1] + (yz & 1), qz = pg[2] + (yz >> 1);
-        const uint32_t r0 = pg[0] + qy * u.res + qz * u.res2;
-        const uint32_t i0 = reduce_idx(r0, u), i1 = reduce_idx(r0 + 1u, u);
+        uint32_t i0, i1;
+        pair_index(pg, yz, u, i0, i1);
         v[2 * yz] = tl[i0];
         v[2 * yz + 1] = tl[i1];
     }
@@ -161,6 +148,7 @@ __global__ void __launch_bounds__(1024) enc_lds_kernel(const float* __restrict__
 // the NEXT chunk it runs MLP slice r of the current one (slice 2cb: density net
 // of column block cb, 2cb+1: its colour net) from a double-buffered LDS row
 // image, so the MFMA / VALU work sits inside the gathers' latency.
+constexpr int XROW = 40;  // halfs per parked encoding row (32 + pad: conflict-free 16-B reads)
 template <bool COLOR, int NW>
 __global__ void __launch_bounds__(64 * NW) fem_pipe_kernel(const float* __restrict__ xyzs,
                                                            const float* __restrict__ dirs, int64_t n,

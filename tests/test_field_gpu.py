@@ -129,12 +129,15 @@ def test_split_encode_mlp_equals_fused(scale):
     assert torch.equal(sig3, HG.density_forward(x, grid, p16)[0])
 
 
-def test_encoding_outside_the_box_wraps_like_tcnn():
+@pytest.mark.parametrize("shrink", [(), (7, 12)])
+def test_encoding_outside_the_box_wraps_like_tcnn(shrink):
     """Inputs outside the grid's box (negative or past-the-end cell coordinates:
     the API takes arbitrary points) index every level modulo its size, as tcnn's
     grid_index does -- each forward kernel (fused field, split encode, the
     trainer's one-launch encode + MLPs) gives the oracle's encoding bit for bit,
-    with no read outside the table."""
+    with no read outside the table.  shrink: hashed levels given a size that is
+    no power of two (2^19 - 8, still a multiple of 8; offsets and table as they
+    are), which only a hand-built descriptor can state: the generic modulo."""
     import ctypes
     f, flat = _oracle_and_params(0.5)
     g = torch.Generator().manual_seed(21)
@@ -144,6 +147,9 @@ def test_encoding_outside_the_box_wraps_like_tcnn():
     d = torch.randn(8192, 3, generator=g)
     n = x.shape[0]
     grid = HG.HashGrid(0.5)
+    for l in shrink:
+        grid.desc.sizes[l] = 2 ** 19 - 8
+        f.spec.sizes[l] = 2 ** 19 - 8
     p16 = flat.to(DEV).half()
     xd, dd = x.to(DEV), d.to(DEV)
     enc_ref = O.hash_encode_fwd(f.spec, x, f.xyz_min, f.xyz_max, f.xyz_params.detach()[f.n_dens:])
