@@ -286,3 +286,120 @@ def field(xyzs, dirs, params, grid, shadow, rgb_act=0):
     """Differentiable fused field (w.r.t. params, and xyzs / dirs where they require grad:
     pose refinement) -> sigmas (n), rgbs (n,3)."""
     return _FieldFn.apply(xyzs, dirs, params, grid, shadow, rgb_act)
+
+
+# ------------------------------------------------------------ exposure tonemappers (DESIGN.md §18)
+TONE_LDR, TONE_RADIANCE, TONE_PARAMS = C["NGP_TONE_LDR"], C["NGP_TONE_RADIANCE"], C["NGP_TONE_PARAMS"]
+TONE_NET = TONE_PARAMS // 3  # one channel: A 64x16 | B 16x64
+
+
+def init_tone_params(generator):
+    """The three tonemapper nets (networks.py:80-93), Xavier-uniform per matrix as init_params does,
+    drawn from `generator` -> (TONE_PARAMS) f32 on the CPU."""
+    parts = []
+    for _ in range(3):
+        for out_d, in_d in ((64, 16), (16, 64)):
+            a = math.sqrt(6.0 / (in_d + out_d))
+            parts.append((torch.rand(out_d * in_d, generator=generator) * 2 - 1) * a)
+    return torch.cat(parts)
+
+
+def tone_exposure(exposure, n, device):
+    """The `exposure` argument of the model surface as the kernels take it -> (tensor | None,
+    n_exposure): None: none; a 0-d / one-element tensor or a number: one value; (n,) / (n,1): per row."""
+    if exposure is None:
+        return None, 0
+    if not isinstance(exposure, torch.Tensor):
+        if not isinstance(exposure, (int, float)):
+            raise ValueError(f"exposure must be a tensor or a number, got {type(exposure).__name__}")
+        exposure = torch.tensor(float(exposure))
+    if exposure.numel() == 1:
+        return exposure.detach().reshape(1).to(device=device, dtype=torch.float32), 1
+    if exposure.shape in ((n,), (n, 1)):
+        return exposure.detach().reshape(n).to(device=device, dtype=torch.float32).contiguous(), n
+    raise ValueError(f"exposure must have one element or shape ({n},) / ({n}, 1), got {tuple(exposure.shape)}")
+
+
+def _tone_args(log_rad, exposure, n_exposure, tone16, mode):
+    n = log_rad.shape[0]
+    _check(log_rad, "log_rad", torch.float32, 3 * n)
+    if mode == TONE_LDR:
+        _check(tone16, "tone16", torch.float16, TONE_PARAMS)
+    if n_exposure:
+        _check(exposure, "exposure", torch.float32)
+        if n_exposure not in (1, n) or exposure.numel() != n_exposure:
+            raise RuntimeError(f"exposure must hold 1 or {n} values, got {exposure.numel()} for n_exposure {n_exposure}")
+    return n
+
+
+def tonemap_forward(log_rad, exposure, n_exposure, tone16, mode=TONE_LDR, n_dev=None, sample_idx=None, out=None):
+    """ngp_tonemap_forward: log radiance (n,3) -> rgbs (n,3) (`out`: written in place on the counted /
+    listed rows, and may be log_rad; None: a new tensor, zero on the other rows)."""
+    n = _tone_args(log_rad, exposure, n_exposure, tone16, mode)
+    if sample_idx is not None:
+        _check(sample_idx, "sample_idx", torch.int32)
+        if n_dev is None:
+            raise RuntimeError("sample_idx needs its count in n_dev")
+    if out is None:
+        out = torch.zeros_like(log_rad) if (n_dev is not None) else torch.empty_like(log_rad)
+    else:
+        _check(out, "rgbs", torch.float32, 3 * n)
+    _K().ngp_tonemap_forward(log_rad, exposure if n_exposure else None, n_exposure, n, n_dev, sample_idx,
+                             tone16 if mode == TONE_LDR else None, int(mode), out, vren._stream())
+    return out
+
+
+def tonemap_backward(log_rad, exposure, n_exposure, tone16, dL_drgbs, grad_tone, n_dev=None, out=None, workspace=None):
+    """ngp_tonemap_backward -> dL/dlog_rad (n,3) (`out`, which may be dL_drgbs); dL/dtone is ADDED to
+    grad_tone (TONE_PARAMS f32)."""
+    n = _tone_args(log_rad, exposure, n_exposure, tone16, TONE_LDR)
+    _check(dL_drgbs, "dL_drgbs", torch.float32, 3 * n)
+    _check(grad_tone, "grad_tone", torch.float32, TONE_PARAMS)
+    if out is None:
+        out = torch.zeros_like(log_rad) if (n_dev is not None) else torch.empty_like(log_rad)
+    else:
+        _check(out, "dL_dlog_rad", torch.float32, 3 * n)
+    if n == 0:
+        return out
+    nbytes = _K().ngp_tonemap_backward_workspace(n)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 3) // 4, device=log_rad.device)
+    elif workspace.numel() * workspace.element_size() < nbytes:
+        raise RuntimeError(f"workspace must hold {nbytes} bytes")
+    _K().ngp_tonemap_backward(log_rad, exposure if n_exposure else None, n_exposure, n, n_dev, tone16, dL_drgbs, out,
+                              grad_tone, workspace, vren._stream())
+    return out
+
+
+class _ToneFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, log_rad, tone_params, exposure, n_exposure, shadow):
+        t16 = shadow.get()
+        log_rad = log_rad.float().contiguous()
+        ctx.save_for_backward(log_rad, exposure)
+        ctx.t16, ctx.n_exposure = t16, n_exposure
+        return tonemap_forward(log_rad, exposure, n_exposure, t16)
+
+    @staticmethod
+    def backward(ctx, drgb):
+        log_rad, exposure = ctx.saved_tensors
+        need_x, need_t = ctx.needs_input_grad[:2]
+        grad = torch.zeros(TONE_PARAMS, device=log_rad.device)
+        dx = tonemap_backward(log_rad, exposure, ctx.n_exposure, ctx.t16, drgb.float().contiguous(), grad)
+        return (dx if need_x else None), (grad if need_t else None), None, None, None
+
+
+def tonemap(log_rad, exposure, tone_params, shadow, mode=TONE_LDR):
+    """The tonemappers on log radiance (n,3) -> rgbs (n,3), differentiable in log_rad and tone_params
+    (not in the exposure: it is data).  exposure: as tone_exposure takes it.  mode TONE_RADIANCE
+    (output_radiance): exp(clamp(x, 0, 20)), forward only."""
+    exposure, n_exposure = tone_exposure(exposure, log_rad.shape[0], log_rad.device)
+    wants_grad = torch.is_grad_enabled() and (log_rad.requires_grad or tone_params.requires_grad)
+    if mode == TONE_RADIANCE:
+        if torch.is_grad_enabled() and log_rad.requires_grad:
+            raise NotImplementedError("output_radiance is forward-only: the radiance mode of the tonemapper has no "
+                                      "backward (call it under torch.no_grad())")
+        return tonemap_forward(log_rad.detach().float().contiguous(), None, 0, None, TONE_RADIANCE)
+    if wants_grad:
+        return _ToneFn.apply(log_rad, tone_params, exposure, n_exposure, shadow)
+    return tonemap_forward(log_rad.detach().float().contiguous(), exposure, n_exposure, shadow.get())

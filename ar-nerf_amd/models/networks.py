@@ -3,7 +3,9 @@ kernels.  tinycudann's three modules are replaced by one fused field
 (hashgrid.py) over a single flat fp32 master parameter:
     params = [W1 | W2 | W3 | W4 | W5 | hash table]
 (`xyz_encoder.params` of tcnn = [W1 | W2 | table]; `rgb_net.params` =
-[W3 | W4 | W5]; see load_tcnn_params / tcnn_params for the mapping)."""
+[W3 | W4 | W5]; see load_tcnn_params / tcnn_params for the mapping).  A
+model built with use_exposure=True also holds the three exposure tonemappers
+as one flat `tone_params` (`tonemapper_net_{0,1,2}.params`)."""
 import numpy as np
 import torch
 from torch import nn
@@ -47,15 +49,19 @@ class _DensityFn(torch.autograd.Function):
 class NGP(nn.Module):
     """models/networks.py:12-281."""
 
-    def __init__(self, scale, rgb_act='Sigmoid', use_raw_HDR=False, seed=4):
+    def __init__(self, scale, rgb_act='Sigmoid', use_raw_HDR=False, seed=4, use_exposure=False):
         super().__init__()
         if rgb_act not in ('Sigmoid', 'None'):
             raise NotImplementedError(f"rgb_act={rgb_act!r}: the reference builds 'Sigmoid' or 'None' (networks.py:68-78)")
-        if rgb_act == 'None' and not use_raw_HDR:
-            raise NotImplementedError("rgb_act='None' without use_raw_HDR needs the exposure tonemapper nets "
-                                      "(networks.py:80-93, 110-131), which are out of scope")
+        if use_exposure and (rgb_act != 'None' or use_raw_HDR):
+            raise ValueError("use_exposure=True is the reference's NGP(scale, rgb_act='None', use_raw_HDR=False) "
+                             f"(train.py:76-77); got rgb_act={rgb_act!r}, use_raw_HDR={use_raw_HDR!r}")
+        if rgb_act == 'None' and not use_raw_HDR and not use_exposure:
+            raise NotImplementedError("rgb_act='None' without use_raw_HDR is the exposure-conditioned model with its "
+                                      "tonemapper nets (networks.py:80-93, 110-131): pass use_exposure=True to build it")
         self.rgb_act = rgb_act
         self.use_raw_HDR = use_raw_HDR
+        self.use_exposure = bool(use_exposure)
         self.scale = scale
         self.register_buffer('center', torch.zeros(1, 3))
         self.register_buffer('xyz_min', -torch.ones(1, 3) * scale)
@@ -72,6 +78,13 @@ class NGP(nn.Module):
         self._shadow = HG.FP16Shadow(self.params)
         # optimizers.FusedAdam writes this shadow in its Adam launch (no re-cast before the next forward)
         self.params._ngp_shadow = self._shadow
+        if self.use_exposure:
+            # tonemapper_net_{0,1,2} (networks.py:80-93) as one flat master [T_0 | T_1 | T_2], T_c = [A 64x16 | B 16x64],
+            # drawn from a generator of its own so `params` is what every other mode draws from `seed`
+            gen = torch.Generator().manual_seed(seed + 1)
+            self.tone_params = nn.Parameter(HG.init_tone_params(gen))
+            self._tone_shadow = HG.FP16Shadow(self.tone_params)
+            self.tone_params._ngp_shadow = self._tone_shadow
 
     # -------------------------------------------------- tcnn param mapping
     def tcnn_params(self):
@@ -104,16 +117,41 @@ class NGP(nn.Module):
         on a sigmoid model use_raw_HDR's leaky_relu is the identity."""
         if self.rgb_act == 'Sigmoid':
             return HG.RGB_SIGMOID
+        if self.use_exposure:  # the colour net's raw output is log radiance; the tonemappers follow (tone_mode)
+            return HG.RGB_NONE
         return HG.RGB_RELU if output_radiance else HG.RGB_LEAKY_RELU
 
+    def tone_mode(self, output_radiance=False):
+        """The tonemap kernels' mode (HG.TONE_*) after the field of a forward call, None for a
+        model without use_exposure (networks.py:158-163)."""
+        if not self.use_exposure:
+            return None
+        return HG.TONE_RADIANCE if output_radiance else HG.TONE_LDR
+
+    def log_radiance_to_rgb(self, log_radiances, **kwargs):
+        """networks.py:110-131: log radiance (N,3) -> LDR rgbs (N,3) through the three tonemapper nets at
+        kwargs['exposure'] (absent / None: unit exposure; one element: uniform; (N,) / (N,1): per sample)."""
+        if not self.use_exposure:
+            raise RuntimeError("log_radiance_to_rgb needs a model built with use_exposure=True")
+        return HG.tonemap(log_radiances, kwargs.get('exposure', None), self.tone_params, self._tone_shadow)
+
     def forward(self, x, d, **kwargs):
-        """networks.py:133-165 -> sigmas (N) f32, rgbs (N,3) f32 (Sigmoid, or the
-        raw-HDR branch: leaky_relu / relu with output_radiance=True)."""
+        """networks.py:133-165 -> sigmas (N) f32, rgbs (N,3) f32 (Sigmoid; the
+        raw-HDR branch: leaky_relu / relu with output_radiance=True; or, with
+        use_exposure, the tonemapped log radiance at kwargs['exposure'] / the
+        radiance exp(clamp(., 0, 20)) with output_radiance=True)."""
         x, d = x.float().contiguous(), d.float().contiguous()
-        act = self.rgb_mode(kwargs.get('output_radiance', False))
+        radiance = kwargs.get('output_radiance', False)
+        act = self.rgb_mode(radiance)
         if torch.is_grad_enabled() and (self.params.requires_grad or x.requires_grad or d.requires_grad):
-            return HG.field(x, d, self.params, self.grid, self._shadow, act)
-        sig, rgb, _, _ = HG.field_forward(x, d, self.grid, self._shadow.get(), save_enc=False, rgb_act=act)
+            sig, rgb = HG.field(x, d, self.params, self.grid, self._shadow, act)
+        else:
+            sig, rgb, _, _ = HG.field_forward(x, d, self.grid, self._shadow.get(), save_enc=False, rgb_act=act)
+        if self.use_exposure:
+            if radiance:
+                rgb = HG.tonemap(rgb, None, self.tone_params, self._tone_shadow, HG.TONE_RADIANCE)
+            else:
+                rgb = self.log_radiance_to_rgb(rgb, **kwargs)
         return sig, rgb
 
     # ---------------------------------------------------- occupancy grid

@@ -66,26 +66,41 @@ def _background(kwargs, rays_d, default):
     return default
 
 
-def _test_renderer(model, n_rays, esf, T_threshold, max_samples, rgb_act=0):
+def _test_renderer(model, n_rays, esf, T_threshold, max_samples, rgb_act=0, tone_mode=None):
     """TestRenderer cached on the model per (rays, loop settings, bitfield,
-    colour mode: the mode is baked into the captured graphs)."""
+    colour mode, tonemap mode: the modes are baked into the captured graphs)."""
     import renderer as RD
     cache = model.__dict__.setdefault('_test_renderers', {})
-    key = (n_rays, float(esf), float(T_threshold), int(max_samples), model.density_bitfield.data_ptr(), int(rgb_act))
+    key = (n_rays, float(esf), float(T_threshold), int(max_samples), model.density_bitfield.data_ptr(), int(rgb_act),
+           tone_mode)
     rr = cache.get(key)
     p16 = model._shadow.get()
+    t16 = model._tone_shadow.get() if tone_mode is not None else None
     if rr is None:
         if len(cache) >= 4:
             cache.clear()
         rr = RD.TestRenderer(n_rays, model.grid, p16.clone(), model.density_bitfield, model.cascades, model.scale,
                              model.grid_size, exp_step_factor=esf, T_threshold=T_threshold, max_samples=max_samples,
-                             iters_per_graph=16, iters_tail=8, rgb_act=int(rgb_act))
-        rr._src = None
+                             iters_per_graph=16, iters_tail=8, rgb_act=int(rgb_act),
+                             tone16=None if t16 is None else t16.clone(), tone_mode=tone_mode)
+        rr._src = rr._tone_src = None
         cache[key] = rr
     if rr._src is not p16:  # parameters changed since the last frame: refresh the renderer's copy
         rr.params16.copy_(p16)
         rr._src = p16
+    if t16 is not None and rr._tone_src is not t16:  # (the tone shadow likewise)
+        rr.tone16.copy_(t16)
+        rr._tone_src = t16
     return rr
+
+
+def _frame_exposure(kwargs):
+    """The `exposure` kwarg of a test-time frame for the device loop: None or one value
+    (the viewer's slider, show_gui.py:86); per-ray exposures take the host loop."""
+    e = kwargs.get('exposure', None)
+    if e is None or not isinstance(e, torch.Tensor) or e.numel() == 1:
+        return True, e
+    return False, e
 
 
 @torch.no_grad()
@@ -96,10 +111,15 @@ def __render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
     GPU the loop runs device-resident in HIP graphs (renderer.TestRenderer,
     bit-identical results); device_loop=False keeps the host-driven loop."""
     exp_step_factor = kwargs.get('exp_step_factor', 0.)
-    if kwargs.get('device_loop', True) and hasattr(model, '_shadow') and rays_o.is_cuda and len(rays_o) > 0:
+    tone_mode = model.tone_mode(kwargs.get('output_radiance', False)) if hasattr(model, 'tone_mode') else None
+    uniform, exposure = _frame_exposure(kwargs) if tone_mode is not None else (True, None)
+    if kwargs.get('device_loop', True) and hasattr(model, '_shadow') and rays_o.is_cuda and len(rays_o) > 0 \
+            and uniform:
         rr = _test_renderer(model, len(rays_o), exp_step_factor, kwargs.get('T_threshold', 1e-4),
                             kwargs.get('max_samples', MAX_SAMPLES),
-                            model.rgb_mode(kwargs.get('output_radiance', False)))
+                            model.rgb_mode(kwargs.get('output_radiance', False)), tone_mode)
+        if tone_mode is not None:
+            rr.set_exposure(exposure)
         # SH_bkg: blended by the frame's closing launch (ngp_render_test_finish_sh)
         bg_sh = _sh_light(kwargs, rays_o.device)
         out = rr.render(rays_o, rays_d, hits_t[:, 0], bg_sh=bg_sh)

@@ -108,7 +108,9 @@ def sh_probes(model, pts, dirs=None, n_rays=2048, SH_bkg=None, blend_bkg=True, p
     the rays (clamped at zero) unless blend_bkg is False.  render_kwargs:
     T_threshold, max_samples, exp_step_factor, output_radiance, as render()
     takes them (output_radiance: a raw-HDR model's relu radiance, what
-    generate_SH_probes asks for under use_EXR).
+    generate_SH_probes asks for under use_EXR; on a model built with
+    use_exposure, the tonemapped colour at the one `exposure` given, unit by
+    default, or its radiance).
 
     Returns {'rgb_sh': (P,9,3), 'trans_sh': (P,9,1)}: the projections of the
     radiance and of 1 - opacity; with return_rays also 'rgb' (P,R,3),
@@ -125,7 +127,7 @@ def sh_probes(model, pts, dirs=None, n_rays=2048, SH_bkg=None, blend_bkg=True, p
     still alive, so a probe's rays are NOT independent of the batch they are
     rendered in: another probes_per_batch gives slightly different values.
     """
-    unknown = set(render_kwargs) - {'T_threshold', 'max_samples', 'exp_step_factor', 'output_radiance'}
+    unknown = set(render_kwargs) - {'T_threshold', 'max_samples', 'exp_step_factor', 'output_radiance', 'exposure'}
     if unknown:
         raise TypeError(f"sh_probes: unexpected arguments {sorted(unknown)}")
     if not hasattr(model, '_shadow'):
@@ -154,7 +156,10 @@ def sh_probes(model, pts, dirs=None, n_rays=2048, SH_bkg=None, blend_bkg=True, p
         bg_sh = torch.as_tensor(SH_bkg, dtype=torch.float32, device=dev).reshape(9, 3).contiguous()
     rr = RND._test_renderer(model, B * R, render_kwargs.get('exp_step_factor', 0.),
                             render_kwargs.get('T_threshold', 1e-4), render_kwargs.get('max_samples', RND.MAX_SAMPLES),
-                            model.rgb_mode(render_kwargs.get('output_radiance', False)))
+                            model.rgb_mode(render_kwargs.get('output_radiance', False)),
+                            model.tone_mode(render_kwargs.get('output_radiance', False)))
+    if rr.tone_mode is not None:
+        rr.set_exposure(render_kwargs.get('exposure', None))
     rgb_sh = torch.empty(n_batches * B, 9, 3, device=dev)
     trans_sh = torch.empty(n_batches * B, 9, device=dev)
     rays = {'rgb': [], 'opacity': []}

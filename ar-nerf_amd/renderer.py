@@ -10,6 +10,8 @@ TestRenderer runs the same loop with every decision in device memory
 (include/ngp_amd.h "device-resident test-time render"): one iteration is
   ngp_render_test_march   (loop test, N_samples, march, valid-sample list)
   ngp_field_encode_mlp over the list (NGP.forward: encode + MLPs in one launch)
+  [ngp_tonemap_forward over the same list, in place on the colours: a model
+   built with use_exposure, whose field output is log radiance]
   ngp_render_test_composite (composite_test_fw + survivor compaction)
 and the iterations are captured in HIP graphs: a frame is graph A (begin +
 summary + `iters_per_graph` iterations), then graph B (`iters_tail` more)
@@ -42,7 +44,7 @@ class TestRenderer:
 
     def __init__(self, n_rays, grid: HG.HashGrid, params16, density_bitfield, cascades, scale, grid_size=128,
                  exp_step_factor=0.0, T_threshold=1e-4, max_samples=MAX_SAMPLES, iters_per_graph=16,
-                 bg_rgb=(0.0, 0.0, 0.0), use_graphs=True, iters_tail=None, rgb_act=0):
+                 bg_rgb=(0.0, 0.0, 0.0), use_graphs=True, iters_tail=None, rgb_act=0, tone16=None, tone_mode=None):
         iters_tail = iters_per_graph if iters_tail is None else iters_tail
         if min(iters_per_graph, iters_tail) < 2 or iters_per_graph % 2 or iters_tail % 2:
             raise ValueError("iters_per_graph / iters_tail must be even (alive lists alternate per iteration)")
@@ -50,6 +52,22 @@ class TestRenderer:
             raise ValueError(f"rgb_act must be one of hashgrid.RGB_*, got {rgb_act}")
         self.rgb_act = int(rgb_act)  # colour-output mode of the field (baked into the captured graphs)
         dev = params16.device
+        # exposure tonemappers between the field and the composite: tone16 is read through
+        # a stable buffer like params16, the exposure through a one-element device buffer (set_exposure)
+        self.tone_mode = None if tone_mode is None else int(tone_mode)
+        self.tone16 = tone16
+        if self.tone_mode is not None:
+            if self.tone_mode not in (HG.TONE_LDR, HG.TONE_RADIANCE):
+                raise ValueError(f"tone_mode must be hashgrid.TONE_LDR / TONE_RADIANCE or None, got {tone_mode}")
+            if self.rgb_act != HG.RGB_NONE:
+                raise ValueError("the tonemappers take the colour net's raw output: rgb_act must be hashgrid.RGB_NONE")
+            if self.tone_mode == HG.TONE_LDR:
+                vren._check("tone16", tone16, torch.float16)
+                if tone16.numel() != HG.TONE_PARAMS:
+                    raise ValueError(f"tone16 must hold {HG.TONE_PARAMS} values, got {tone16.numel()}")
+        elif tone16 is not None:
+            raise ValueError("tone16 needs a tone_mode")
+        self.exposure = torch.ones(1, dtype=torch.float32, device=dev)
         vren._check("params16", params16, torch.float16)
         vren._check("density_bitfield", density_bitfield, torch.uint8)
         self.n_rays, self.grid, self.params16, self.bitfield = int(n_rays), grid, params16, density_bitfield
@@ -100,6 +118,9 @@ class TestRenderer:
         K.ngp_field_encode_mlp_act(self.xyzs, self.dirs, self.cap, self.n_valid, self.sample_idx, self.grid.desc,
                                    self.params16[HG.MLP_PARAMS:], self.params16, None, self.sigmas, self.rgbs, None,
                                    self.rgb_act, s)
+        if self.tone_mode is not None:  # log radiance -> colour on the valid samples (networks.py:158-163)
+            K.ngp_tonemap_forward(self.rgbs, self.exposure, 1, self.cap, self.n_valid, self.sample_idx, self.tone16,
+                                  self.tone_mode, self.rgbs, s)
         K.ngp_render_test_composite(self.sigmas, self.rgbs, self.deltas, self.ts, self.n_eff, self.n_rays, par,
                                     self.state, self.alive[par], self.alive[par ^ 1], self.T_threshold, self.opacity,
                                     self.depth, self.rgb, s)
@@ -161,6 +182,18 @@ class TestRenderer:
         self.hits_t.copy_(hits_t.reshape(-1, 2))
         return self.render_loaded(bg_sh)
 
+    def set_exposure(self, e):
+        """The frame's exposure (a number or a one-element tensor; None: unit): written to the device
+        scalar the captured tonemap launches read, so the next frame follows it without re-capture."""
+        if e is None:
+            self.exposure.fill_(1.0)
+        elif isinstance(e, torch.Tensor):
+            if e.numel() != 1:
+                raise ValueError(f"the device loop takes one exposure per frame, got {tuple(e.shape)}")
+            self.exposure.copy_(e.detach().reshape(1))
+        else:
+            self.exposure.fill_(float(e))
+
     def set_camera(self, directions, center, half_size):
         """Per-pixel camera directions (H*W, 3) (datasets/ray_utils.py:7-42)
         and the scene box, for render_pose."""
@@ -189,5 +222,8 @@ def for_model(model, n_rays, output_radiance=False, **kwargs):
     """TestRenderer over a models.networks.NGP (its fp16 shadow and bitfield;
     the model's colour mode, relu for a raw-HDR model with output_radiance)."""
     kwargs.setdefault('rgb_act', model.rgb_mode(output_radiance))
+    if getattr(model, 'use_exposure', False):  # (its tone shadow in place: refresh with rr.tone16.copy_)
+        kwargs.setdefault('tone_mode', model.tone_mode(output_radiance))
+        kwargs.setdefault('tone16', model._tone_shadow.get())
     return TestRenderer(n_rays, model.grid, model._shadow.get(), model.density_bitfield, model.cascades,
                         model.scale, model.grid_size, **kwargs)

@@ -4,6 +4,8 @@ key mapping between the reference's tcnn modules and models.networks.NGP:
   reference state_dict (Lightning 'state_dict', prefix 'model.')   NGP here
   xyz_encoder.params  = [W1 64x32 | W2 16x64 | hash table]          params[:3072] + params[10240:]
   rgb_net.params      = [W3 64x32 | W4 64x64 | W5 16x64]            params[3072:10240]
+  tonemapper_net_{0,1,2}.params = [A 64x16 | B 16x64] each          tone_params[2048 i : 2048 (i + 1)]
+    (models built with use_exposure only; networks.py:80-93)
   center, xyz_min, xyz_max, half_size, density_bitfield,            same-named buffers
   density_grid, grid_coords (train.py:79-82)                        buffers when present
 
@@ -19,6 +21,8 @@ TCNN_KEYS = ("xyz_encoder.params", "rgb_net.params")
 # Parameter -- the SH dir_encoder (models/networks.py:59-66) -- so every
 # reference checkpoint holds 'model.dir_encoder.params' of shape [0]
 EMPTY_TCNN_KEYS = ("dir_encoder.params",)
+TONE_KEYS = tuple(f"tonemapper_net_{i}.params" for i in range(3))
+TONE_NET = 2048
 
 
 def _load(ckpt_path):
@@ -43,11 +47,15 @@ def extract_model_state_dict(ckpt_path, model_name='model', prefixes_to_ignore=[
 
 def tcnn_state_dict(model):
     """NGP state in the reference's key layout (loadable by its load_ckpt)."""
-    sd = {k: v for k, v in model.state_dict().items() if k != 'params'}
+    sd = {k: v for k, v in model.state_dict().items() if k not in ('params', 'tone_params')}
     xyz, rgb = model.tcnn_params()
     sd['xyz_encoder.params'] = xyz.clone()
     sd['rgb_net.params'] = rgb.clone()
     sd['dir_encoder.params'] = torch.zeros(0, dtype=rgb.dtype)
+    if getattr(model, 'use_exposure', False):
+        tone = model.tone_params.detach()
+        for i, k in enumerate(TONE_KEYS):
+            sd[k] = tone[TONE_NET * i:TONE_NET * (i + 1)].clone()
     for name in ('density_grid', 'grid_coords'):
         if hasattr(model, name) and name not in sd:
             sd[name] = getattr(model, name)
@@ -65,6 +73,20 @@ def load_ckpt(model, ckpt_path, model_name='model', prefixes_to_ignore=[]):
     ck = extract_model_state_dict(ckpt_path, model_name, prefixes_to_ignore)
     if all(k in ck for k in TCNN_KEYS):
         model.load_tcnn_params(ck.pop(TCNN_KEYS[0]), ck.pop(TCNN_KEYS[1]))
+    have = [k for k in TONE_KEYS if k in ck]
+    if getattr(model, 'use_exposure', False):
+        if have or 'tone_params' not in ck:  # (a checkpoint of this model's own state_dict carries tone_params)
+            if len(have) != len(TONE_KEYS):
+                raise RuntimeError(f"checkpoint lacks {[k for k in TONE_KEYS if k not in ck]} for a model built "
+                                   "with use_exposure=True")
+            tone = [ck.pop(k) for k in TONE_KEYS]
+            if any(t.numel() != TONE_NET for t in tone):
+                raise RuntimeError(f"checkpoint entries {list(TONE_KEYS)} should hold {TONE_NET} values each, have "
+                                   f"{[t.numel() for t in tone]}")
+            model.tone_params.copy_(torch.cat([t.reshape(-1) for t in tone]).to(model.tone_params))
+    elif have:
+        raise RuntimeError(f"checkpoint holds {have} (an exposure-conditioned model): build the model with "
+                           "use_exposure=True to load it")
     for k in EMPTY_TCNN_KEYS:  # parameter-free tcnn encodings: nothing to load
         if k in ck:
             if ck[k].numel() != 0:

@@ -933,6 +933,54 @@ int ngp_occupancy_keep(const int64_t* flat_idx, int64_t M, int64_t cell_base, in
 int ngp_density_scatter_kept(const int32_t* list, const int64_t* count, int64_t n_max, const int64_t* indices,
                              const float* sigmas, int64_t pos_base, uint64_t* grid_key, void* stream);
 
+/* ---- exposure tonemappers (HDR-NeRF mode) --------------------------------
+ * NGP(rgb_act='None', use_raw_HDR=False) of the reference: the colour net's
+ * output is log-radiance and three per-channel 1 -> 64 -> 1 networks
+ * (tonemapper_net_{0,1,2}: ReLU, output Sigmoid; networks.py:80-93, 110-131)
+ * map it to an LDR colour per sample.  DESIGN.md §18 is the definition; in short,
+ * per channel c with T_c = [A 64x16 | B 16x64] (fp16, row-major [out][in]),
+ * tone_f16 = [T_0 | T_1 | T_2] (NGP_TONE_PARAMS halfs), u = x_c + log(e):
+ *   beta_j = A[j,1] + ... + A[j,15]      (the padded inputs are 1; ascending, fp32)
+ *   a_j = fmaf(A[j,0], u, beta_j),  r_j = a_j > 0 ? a_j : 0,  z = sum_j B[0,j] r_j
+ *   y_c = 1 / (1 + exp(-z))
+ * NGP_TONE_RADIANCE (output_radiance, networks.py:159-161): y = exp(min(max(x,
+ * 0), 20)); no parameters, no exposure, forward only. */
+#define NGP_TONE_LDR 0
+#define NGP_TONE_RADIANCE 1
+#define NGP_TONE_PARAMS 6144
+
+/* rgbs (n,3) = tonemap(log_rad (n,3)) over the rows [0, min(n, *n_dev))
+ * (n_dev null: n), or over the rows sample_idx[i], i < min(n, *n_dev) (the pair
+ * ngp_field_encode_mlp_act takes; an index outside [0, n) is skipped).  Every
+ * other row of rgbs keeps its bits; rgbs may be log_rad (in place).
+ * exposure: n_exposure values, n_exposure = 0 (none: e = 1), 1 (one value,
+ * read from device memory when the kernel runs, so a captured graph follows
+ * it) or n (one per row).  n == 0: no-op.  NGP_EINVAL, nothing launched: a
+ * mode outside the two above, n < 0, n_exposure not in {0, 1, n}, a null
+ * log_rad / rgbs, a null exposure with n_exposure > 0, a null tone_f16 in
+ * NGP_TONE_LDR, sample_idx without n_dev. */
+int ngp_tonemap_forward(const float* log_rad, const float* exposure, int64_t n_exposure, int64_t n,
+                        const int64_t* n_dev, const int32_t* sample_idx, const void* tone_f16, int mode,
+                        float* rgbs, void* stream);
+/* Backward of NGP_TONE_LDR over the rows [0, min(n, *n_dev)), the hidden layer
+ * recomputed from log_rad: dL_dlog_rad (n,3) is written (it may be dL_drgbs;
+ * rows past the count are left alone) and dL/dtone is ADDED to grad_tone
+ * (NGP_TONE_PARAMS f32, layout of tone_f16): with delta = g y (1 - y), m_j =
+ * [a_j > 0], S0_j = sum m_j delta, S1_j = sum m_j delta u over the rows,
+ *   dB[0,j] += A[j,0] S1_j + beta_j S0_j,  dA[j,0] += B[0,j] S1_j,
+ *   dA[j,k] += B[0,j] S0_j for every k = 1..15 (the implied bias),
+ * rows 1..15 of B untouched; dL/dx_c = delta sum_j m_j B[0,j] A[j,0].  A row
+ * whose dL_drgbs is 0 adds exactly nothing.  No atomics: per-workgroup partial
+ * sums go to `workspace` (ngp_tonemap_backward_workspace(n) bytes, 16-byte
+ * aligned) and a second kernel adds them in workgroup order, so two runs give
+ * the same bits.  No gradient to the exposure.  n == 0: no-op.  NGP_EINVAL as
+ * above, and for a null tone_f16 / dL_drgbs / dL_dlog_rad / grad_tone /
+ * workspace. */
+size_t ngp_tonemap_backward_workspace(int64_t n);
+int ngp_tonemap_backward(const float* log_rad, const float* exposure, int64_t n_exposure, int64_t n,
+                         const int64_t* n_dev, const void* tone_f16, const float* dL_drgbs, float* dL_dlog_rad,
+                         float* grad_tone, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
