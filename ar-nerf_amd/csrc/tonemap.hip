@@ -17,46 +17,14 @@
 //    reductions, no atomics.  The workgroup's sums go to its slot of the
 //    workspace; tonemap_fold_kernel adds the slots in workgroup order, forms
 //    the three gradients per unit and adds them into grad_tone.
+// The arithmetic itself is tonemap.h's, shared with the training step's row
+// and list forms (tonemap_step.hip).
 #pragma clang fp contract(off)
 
 #include "common.h"
+#include "tonemap.h"
 
 namespace ngp {
-
-constexpr int TM_THREADS = 256;
-constexpr int TM_WAVES = TM_THREADS / 64;
-constexpr int TM_NET = 2048;           // one channel's parameters: A 64x16 | B 16x64
-constexpr int TM_B = 1024;             // offset of B in a channel
-constexpr int TM_SLOT = 3 * 2 * 64;    // one workgroup's partial sums: [channel][S0, S1][unit]
-constexpr int TM_FWD_BLOCKS = 2048;    // grid caps: the grids do not grow with n
-constexpr int TM_BWD_BLOCKS = 512;
-
-// beta_j: the fifteen padded inputs are 1 (ascending k, fp32)
-__device__ __forceinline__ float tm_beta(const _Float16* __restrict__ A, int j) {
-    float beta = (float)A[j * 16 + 1];
-#pragma unroll
-    for (int k = 2; k < 16; ++k) beta += (float)A[j * 16 + k];
-    return beta;
-}
-
-// LDS image of the three networks: per (channel, unit) {A_j0, beta_j, B_0j, B_0j * A_j0}
-__device__ __forceinline__ void tm_load_weights(const _Float16* __restrict__ tone, float4 (*w)[64]) {
-    for (int t = threadIdx.x; t < 192; t += TM_THREADS) {
-        const int c = t >> 6, j = t & 63;
-        const _Float16* T = tone + c * TM_NET;
-        const float a0 = (float)T[j * 16], b = (float)T[TM_B + j];
-        w[c][j] = make_float4(a0, tm_beta(T, j), b, b * a0);
-    }
-    __syncthreads();
-}
-
-__device__ __forceinline__ float tm_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
-
-// log of the row's exposure (n_exposure: 0 none, 1 one value, else one per row)
-__device__ __forceinline__ float tm_log_exposure(const float* __restrict__ exposure, int64_t n_exposure, int64_t row) {
-    if (n_exposure == 0) return 0.0f;
-    return logf(exposure[n_exposure == 1 ? 0 : row]);
-}
 
 __global__ void __launch_bounds__(TM_THREADS) tonemap_forward_kernel(const float* log_rad,
                                                                     const float* __restrict__ exposure,
@@ -82,19 +50,7 @@ __global__ void __launch_bounds__(TM_THREADS) tonemap_forward_kernel(const float
 #pragma unroll
             for (int c = 0; c < 3; ++c) y[c] = expf(fminf(fmaxf(x[c], 0.0f), 20.0f));
         } else {
-            const float le = tm_log_exposure(exposure, n_exposure, row);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float u = x[c] + le;
-                float z = 0.0f;
-#pragma unroll 8
-                for (int j = 0; j < 64; ++j) {
-                    const float4 p = w[c][j];
-                    const float a = fmaf(p.x, u, p.y);
-                    z = fmaf(p.z, a > 0.0f ? a : 0.0f, z);
-                }
-                y[c] = tm_sigmoid(z);
-            }
+            tm_forward_row(w, x, tm_log_exposure(exposure, n_exposure, row), y);
         }
 #pragma unroll
         for (int c = 0; c < 3; ++c) rgbs[3 * row + c] = y[c];
@@ -134,18 +90,9 @@ __global__ void __launch_bounds__(TM_THREADS) tonemap_backward_kernel(const floa
             if (live) {
                 const float g = dL_drgbs[3 * row + c];
                 u = log_rad[3 * row + c] + le;
-                float z = 0.0f, ba = 0.0f;
-#pragma unroll 8
-                for (int j = 0; j < 64; ++j) {
-                    const float4 p = w[c][j];
-                    const float a = fmaf(p.x, u, p.y);
-                    const bool on = a > 0.0f;
-                    z = fmaf(p.z, on ? a : 0.0f, z);
-                    ba += on ? p.w : 0.0f;
-                }
-                const float y = tm_sigmoid(z);
-                delta = g == 0.0f ? 0.0f : g * (y * (1.0f - y));
-                dL_dlog_rad[3 * row + c] = delta * ba;
+                float dx;
+                tm_backward_channel(w[c], u, g, delta, dx);
+                dL_dlog_rad[3 * row + c] = dx;
                 if (delta == 0.0f) u = 0.0f;  // (adds nothing whatever its input holds: 0 * NaN must not reach S1)
             }
             ud[wv][c][lane] = make_float2(u, delta);
@@ -153,61 +100,15 @@ __global__ void __launch_bounds__(TM_THREADS) tonemap_backward_kernel(const floa
         __syncthreads();
         // phase 2, lane per hidden unit over this wave's rows (a dead row has delta 0)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-#pragma unroll 8
-            for (int r = 0; r < 64; ++r) {
-                const float2 p = ud[wv][c][r];
-                const float d = fmaf(a0[c], p.x, be[c]) > 0.0f ? p.y : 0.0f;
-                s0[c] += d;
-                s1[c] = fmaf(d, p.x, s1[c]);
-            }
-        }
+        for (int c = 0; c < 3; ++c) tm_accumulate(ud[wv][c], a0[c], be[c], s0[c], s1[c]);
         __syncthreads();
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        part[wv][(2 * c) * 64 + lane] = s0[c];
-        part[wv][(2 * c + 1) * 64 + lane] = s1[c];
-    }
-    __syncthreads();
-    for (int t = tid; t < TM_SLOT; t += TM_THREADS) {
-        float s = part[0][t];
-#pragma unroll
-        for (int v = 1; v < TM_WAVES; ++v) s += part[v][t];
-        slots[(int64_t)blockIdx.x * TM_SLOT + t] = s;
-    }
-}
-
-// One thread per (channel, unit): S0, S1 over the slots in workgroup order, then
-// dB_0j = A_j0 S1 + beta_j S0, dA_j0 = B_0j S1, dA_jk = B_0j S0 (k = 1..15), added into grad.
-__global__ void __launch_bounds__(192) tonemap_fold_kernel(const float* __restrict__ slots, int n_slots,
-                                                          const _Float16* __restrict__ tone,
-                                                          float* __restrict__ grad) {
-    const int c = threadIdx.x >> 6, j = threadIdx.x & 63;
-    float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll 8
-    for (int b = 0; b < n_slots; ++b) {
-        s0 += slots[(int64_t)b * TM_SLOT + (2 * c) * 64 + j];
-        s1 += slots[(int64_t)b * TM_SLOT + (2 * c + 1) * 64 + j];
-    }
-    const _Float16* T = tone + c * TM_NET;
-    float* G = grad + c * TM_NET;
-    const float a0 = (float)T[j * 16], beta = tm_beta(T, j), bj = (float)T[TM_B + j];
-    G[TM_B + j] += fmaf(a0, s1, beta * s0);
-    G[j * 16] += bj * s1;
-    const float db = bj * s0;
-#pragma unroll
-    for (int k = 1; k < 16; ++k) G[j * 16 + k] += db;
+    tm_store_slot(part, s0, s1, slots);
 }
 
 }  // namespace ngp
 
 using namespace ngp;
-
-static int64_t tm_bwd_blocks(int64_t n) {
-    const int64_t tiles = (n + TM_THREADS - 1) / TM_THREADS;
-    return tiles < TM_BWD_BLOCKS ? tiles : TM_BWD_BLOCKS;
-}
 
 static bool tm_exposure_ok(const float* exposure, int64_t n_exposure, int64_t n) {
     if (n_exposure != 0 && n_exposure != 1 && n_exposure != n) return false;

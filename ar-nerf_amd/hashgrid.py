@@ -371,6 +371,62 @@ def tonemap_backward(log_rad, exposure, n_exposure, tone16, dL_drgbs, grad_tone,
     return out
 
 
+# ---- the forms the fused training step takes
+def sample_exposure(rays_a, out, img_idxs=None, img_exposure=None, ray_exposure=None):
+    """ngp_sample_exposure / ngp_sample_exposure_rays: every row (ray, start, N) of rays_a writes its
+    ray's exposure -- img_exposure[img_idxs[ray]], or ray_exposure[ray] -- to out[start : start + N];
+    the other slots of `out` (n) f32 keep their bits."""
+    _check(out, "sample_exposure", torch.float32)
+    n_rays, n = rays_a.shape[0], out.numel()
+    if ray_exposure is not None:
+        _check(ray_exposure, "ray_exposure", torch.float32, n_rays)
+        _K().ngp_sample_exposure_rays(rays_a, n_rays, ray_exposure, n, out, vren._stream())
+    else:
+        _check(img_idxs, "img_idxs", torch.int64, n_rays)
+        _check(img_exposure, "img_exposure", torch.float32)
+        _K().ngp_sample_exposure(rays_a, n_rays, img_idxs, img_exposure, img_exposure.numel(), n, out, vren._stream())
+    return out
+
+
+def tonemap_forward_rows(log_rad, rays_a, rows, n_rows_dev, first, exposure, tone16, out):
+    """ngp_tonemap_forward_rows: the first min(N_r, first) samples of the listed rows of rays_a, each at
+    its own exposure (n) -> `out` (n,3), which may be log_rad; every other row of `out` keeps its bits."""
+    n = _tone_args(log_rad, exposure, log_rad.shape[0], tone16, TONE_LDR)
+    _check(out, "rgbs", torch.float32, 3 * n)
+    _K().ngp_tonemap_forward_rows(log_rad, n, rays_a, rows, n_rows_dev, rays_a.shape[0], int(first), exposure, tone16,
+                                  out, vren._stream())
+    return out
+
+
+def tonemap_backward_indexed(log_rad, exposure, tone16, dL_drgbs, grad_tone, n_dev, sample_idx, out, workspace=None):
+    """ngp_tonemap_backward_indexed over the rows sample_idx[:min(n, *n_dev)], each at its own exposure
+    (n) -> dL/dlog_rad on those rows of `out` (which may be dL_drgbs); dL/dtone ADDED to grad_tone."""
+    n = _tone_args(log_rad, exposure, log_rad.shape[0], tone16, TONE_LDR)
+    _check(dL_drgbs, "dL_drgbs", torch.float32, 3 * n)
+    _check(grad_tone, "grad_tone", torch.float32, TONE_PARAMS)
+    _check(out, "dL_dlog_rad", torch.float32, 3 * n)
+    if n == 0:
+        return out
+    nbytes = _K().ngp_tonemap_backward_indexed_workspace(n)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 3) // 4, device=log_rad.device)
+    elif workspace.numel() * workspace.element_size() < nbytes:
+        raise RuntimeError(f"workspace must hold {nbytes} bytes")
+    _K().ngp_tonemap_backward_indexed(log_rad, exposure, n, n_dev, sample_idx, tone16, dL_drgbs, out, grad_tone,
+                                      workspace, vren._stream())
+    return out
+
+
+def unit_exposure_term(tone16, target, grad_tone, out_loss=None):
+    """ngp_unit_exposure_term -> (1) f32: mean_c 0.5 (tonemap(0, exposure 1)_c - target)^2; its gradient
+    ADDED to grad_tone."""
+    _check(tone16, "tone16", torch.float16, TONE_PARAMS)
+    _check(grad_tone, "grad_tone", torch.float32, TONE_PARAMS)
+    out_loss = torch.zeros(1, device=grad_tone.device) if out_loss is None else out_loss
+    _K().ngp_unit_exposure_term(tone16, float(target), grad_tone, out_loss, vren._stream())
+    return out_loss
+
+
 class _ToneFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_rad, tone_params, exposure, n_exposure, shadow):

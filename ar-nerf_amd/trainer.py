@@ -22,6 +22,16 @@ per-ray sums, the per-image chain rule (pose_grad) and a second Adam step the
 corrections -- step N's rays use ext_N, step N + 1's ext_{N+1}, so no batch is
 marched ahead of the pose Adam and its steps run eagerly: use_graphs has no
 effect under it (_pose_state, _pose_backward, _step).
+
+use_exposure (train.py:76-77, 106-107, 182-187 under --use_exposure; off by
+default): the field gives log radiance (`rgbs`), the three
+tonemapper nets turn it and each sample's exposure into the composited colour
+(`ldr`) right after every field launch, over exactly the samples it evaluated;
+after the compositing their backward turns dL/dldr into dL/dlog-radiance in
+place over the gradient-carrying samples and adds into `tone_grad`, the
+unit-exposure term follows, and one more Adam launch steps `tone_params`.  The
+exposure comes per training image (train_step) or per ray (step) and is spread
+to the samples when the batch is marched (_expose).
 """
 from __future__ import annotations
 
@@ -66,13 +76,25 @@ class NGPTrainer:
                  device="cuda", process_group=None, hash_backward="hybrid", bin_samples_per_ray=None, bin_level_lo=None,
                  chunk_first=64, erode=False, lambda_distortion=0.0, bin_merge_hi=None, fused_adam=True, use_graphs=True,
                  pair_steps=False, emulate_dp=False, dp_fine_buckets=2, use_raw_HDR=False, optimize_ext=False,
-                 pose_lr=1e-6):
+                 pose_lr=1e-6, use_exposure=False, unit_exposure_rgb=None):
         self.dev = torch.device(device)
         # raw-HDR model (train.py:76-77: NGP(rgb_act='None', use_raw_HDR=True) under --use_EXR): no
         # colour activation but leaky_relu in training, relu for output_radiance
         # (networks.py:152-157); fp32 ground truth may exceed 1
         self.use_raw_HDR = bool(use_raw_HDR)
         self.rgb_act = HG.RGB_LEAKY_RELU if self.use_raw_HDR else HG.RGB_SIGMOID
+        # exposure-conditioned model (train.py:76-77 under --use_exposure: NGP(rgb_act='None',
+        # use_raw_HDR=False)): the colour net gives log radiance, the three tonemapper nets turn log
+        # radiance + log exposure into the LDR colour that is composited;
+        # unit_exposure_rgb: the target of the unit-exposure term (train.py:182-187), None: no such term
+        self.use_exposure = bool(use_exposure)
+        self.unit_exposure_rgb = None if unit_exposure_rgb is None else float(unit_exposure_rgb)
+        self.tone_params = None
+        if self.use_exposure:
+            if self.use_raw_HDR:
+                raise ValueError("use_exposure=True is the reference's NGP(scale, rgb_act='None', use_raw_HDR=False): "
+                                 "it has no raw-HDR variant (the tonemappers' output is an LDR colour)")
+            self.rgb_act = HG.RGB_NONE
         self.scale = float(scale)
         self.batch_size = batch_size
         self.lr0, self.num_epochs, self.steps_per_epoch = lr, num_epochs, steps_per_epoch
@@ -109,6 +131,14 @@ class NGPTrainer:
             raise NotImplementedError("NGPTrainer(optimize_ext=True) runs the single-process step only: the pose "
                                       "gradient is not reduced across ranks (no process group of more than one "
                                       "rank, no emulate_dp)")
+        if self.use_exposure and self.optimize_ext:
+            raise NotImplementedError("NGPTrainer(use_exposure=True, optimize_ext=True): the pose gradient does not "
+                                      "pass through the tonemappers yet (the field's input gradients would need "
+                                      "dL/dlog-radiance kept beside the pose chain)")
+        if self.use_exposure and self.dp:
+            raise NotImplementedError("NGPTrainer(use_exposure=True) runs the single-process step only: the "
+                                      "tonemappers' gradient has no ZeRO-1 bucket and is not reduced across ranks "
+                                      "(no process group of more than one rank, no emulate_dp)")
         dev = self.dev
         # ---- field parameters: fp32 master, fp16 shadow, Adam state, grad
         self.grid = HG.HashGrid(scale)
@@ -199,6 +229,8 @@ class NGPTrainer:
         # Two sets of ray / march buffers: the next batch is marched on a side
         # stream while the current batch's field, loss, backward and Adam run.
         self.msets = [self._march_buffers(R, cap, f, self.density_bitfield.numel()) for _ in range(2)]
+        if self.use_exposure:
+            self._tone_buffers(seed, R, cap, f)
         self.cur = 0
         self.march_stream = torch.cuda.Stream(device=dev)
         self._pending = None  # (set index, event) of a batch marched ahead
@@ -362,9 +394,62 @@ class NGPTrainer:
                     # (ngp_field_encode_first_coarse, run by the previous step beside its accumulation)
                     pre_ready=False)
 
+    def _tone_buffers(self, seed, R, cap, f):
+        """use_exposure: the tonemappers' fp32 master (drawn as NGP draws it: a generator of its own at
+        seed + 1), fp16 shadow, gradient, Adam moments and the backward's workspace; the tonemapped
+        colours `ldr` beside `rgbs`, which keeps the log radiance (the backward recomputes the hidden
+        layer from it); per march set the exposure of every sample (1 where no row owns the slot) and
+        the table it was filled from (exp_key: host-side, None = not from a table)."""
+        dev = self.dev
+        self.tone_params = HG.init_tone_params(torch.Generator().manual_seed(seed + 1)).to(dev)
+        self.tone16 = self.tone_params.half()
+        self.tone_grad = torch.zeros(HG.TONE_PARAMS, **f)
+        self.tone_exp_avg, self.tone_exp_avg_sq = torch.zeros(HG.TONE_PARAMS, **f), torch.zeros(HG.TONE_PARAMS, **f)
+        self._tone_ws = torch.empty((self.L.ngp_tonemap_backward_indexed_workspace(cap) + 3) // 4, **f)
+        self.ldr = torch.zeros(cap, 3, **f)  # (finite where never evaluated, as rgbs)
+        self.out_loss_unit = torch.zeros(1, **f)
+        self._exp_table = self._ray_exposure = None
+        for m in self.msets:
+            m["sample_exposure"] = torch.ones(cap, **f)
+            m["exp_key"] = None
+
     def _bind(self, m):
         for k, v in m.items():
             setattr(self, k, v)
+
+    # ------------------------------------------------------- exposure (use_exposure)
+    def _exp_key(self):
+        """What identifies the per-image exposure table of train_step, appended to the graph keys next
+        to gt's: (address, length); nothing with the mode off"""
+        if not self.use_exposure:
+            return ()
+        t = self._exp_table
+        return (None,) if t is None else ((t.data_ptr(), int(t.shape[0])),)
+
+    def _check_exposure(self, exposure, n, what):
+        if not self.use_exposure:
+            if exposure is not None:
+                raise ValueError("exposure= needs a trainer built with use_exposure=True")
+            return None
+        if exposure is None:
+            raise ValueError(f"NGPTrainer(use_exposure=True): pass exposure=, {what}")
+        if (not isinstance(exposure, torch.Tensor) or exposure.dtype != torch.float32 or not exposure.is_contiguous()
+                or exposure.device.type != self.dev.type or tuple(exposure.shape) != (n,)):
+            raise ValueError(f"exposure must be a contiguous f32 tensor of shape ({n},) on the device: {what}")
+        return exposure
+
+    def _expose(self, k, s):
+        """sample_exposure of buffer set k from the per-image table and the set's img_idxs (stream s)"""
+        m, t = self.msets[k], self._exp_table
+        self.L.ngp_sample_exposure(m["rays_a"], self.batch_size, m["img_idxs"], t, t.shape[0], self.cap,
+                                   m["sample_exposure"], s)
+        m["exp_key"] = self._exp_key()
+
+    def _tonemap(self, s, total, idx):
+        """LDR colours of the samples a field launch just evaluated: the listed samples idx[:total]
+        (idx None: the range [0, total)), rgbs (log radiance) -> ldr"""
+        self.L.ngp_tonemap_forward(self.rgbs, self.sample_exposure, self.cap, self.cap, total, idx, self.tone16,
+                                   HG.TONE_LDR, self.ldr, s)
 
     # ---- argument groups the launches below share, in the header's order
     @property
@@ -620,7 +705,7 @@ class NGPTrainer:
             else:
                 _, img_idxs, pix_idxs, noise = src
                 assert img_idxs.shape[0] == R
-                if self.optimize_ext:  # (the pose gradient reads the batch's indices from the set)
+                if self.optimize_ext or self.use_exposure:  # (the pose gradient / the exposure lookup read the set's indices)
                     m["img_idxs"].copy_(img_idxs)
                     m["pix_idxs"].copy_(pix_idxs)
                 L.ngp_raygen_aabb(directions, poses, img_idxs, pix_idxs, R, self.center, self.half_size, NEAR_DISTANCE,
@@ -648,6 +733,13 @@ class NGPTrainer:
                 L.ngp_ray_segments_capped(m["rays_a"], R, K, m["act_start1"], m["eval_total1"], None, m["eval_idx1"], s)
             elif rows:
                 L.ngp_rays_nonempty(m["rays_a"], R, m["rows_ne"], m["n_rows_ne"], None, m["eval_total2"], s)
+            if self.use_exposure:
+                # every sample's exposure from the per-image table, here beside the previous step; a batch
+                # given per-ray exposures (step) gets them once it is bound (_step)
+                if src[0] == "sample":
+                    self._expose(k, s)
+                else:
+                    m["exp_key"] = None
             if side:
                 self._ev("march_side", 1, stream)
 
@@ -746,15 +838,17 @@ class NGPTrainer:
         t = [int(v) for v in self.stats.view(STAT_STRIPES, STAT_STRIDE)[:, :3].sum(0).tolist()]
         return t + [int(self.eval_stats[0])]
 
-    def step(self, img_idxs, pix_idxs, rgb_gt, directions, poses, noise=None, apply_adam=True, next_batch=None):
+    def step(self, img_idxs, pix_idxs, rgb_gt, directions, poses, noise=None, apply_adam=True, next_batch=None,
+             exposure=None):
         """One training step on a batch (train.py:174-200).  img/pix (R) i64,
         rgb_gt (R,3) f32, directions (HW,3), poses (n_img,3,4), all on device.
         next_batch = (img, pix) of the following step: marched ahead on the
-        side stream."""
+        side stream.  exposure (use_exposure): the exposure of every ray (R) f32."""
+        self._ray_exposure = self._check_exposure(exposure, self.batch_size, "one value per ray of the batch")
         nxt = None if next_batch is None else ("idx", next_batch[0], next_batch[1], None)
         return self._step(("idx", img_idxs, pix_idxs, noise), rgb_gt, directions, poses, apply_adam, nxt)
 
-    def train_step(self, gt, directions, poses, allow_pair=True):
+    def train_step(self, gt, directions, poses, allow_pair=True, exposure=None):
         """One training step on a batch drawn on device from the training set
         (gt (n_img, HW, 3) u8 images -- or f32 colours, e.g. alpha-blended
         data -- directions (HW,3), poses (n_img,3,4)):
@@ -765,13 +859,19 @@ class NGPTrainer:
         (NGP_GRAPHS=0: always eager).  pair_steps: a call may run this step
         AND the next in one replay (the next call then only advances the
         count); allow_pair=False keeps this call to one step, e.g. the last
-        step of a measured window."""
+        step of a measured window.  exposure (use_exposure): one exposure per
+        training image (n_img) f32 on the device, e.g. rays[:, 0, 3] of an
+        HDR-NeRF set; read when the kernels run, its address part of the graph
+        key like gt's."""
         gs, ui = self.global_step, self.update_interval
         self._throttle()
+        if self.use_exposure or exposure is not None:
+            self._exp_table = self._check_exposure(exposure, gt.shape[0], "one value per training image")
         if self._ran_ahead:  # this step was the second half of the previous call's two-step graph
-            if self._pair_key != (gt.data_ptr(), directions.data_ptr(), poses.data_ptr(), gt.shape, gt.dtype):
+            if self._pair_key != (gt.data_ptr(), directions.data_ptr(), poses.data_ptr(), gt.shape,
+                                  gt.dtype) + self._exp_key():
                 raise RuntimeError("pair_steps: the second step of a two-step graph replay must be given the same "
-                                   "gt / directions / poses as the first (it already ran on them)")
+                                   "gt / directions / poses (/ exposure) as the first (it already ran on them)")
             self._ran_ahead = False
             self.global_step += 1
             return self.out_loss
@@ -826,7 +926,8 @@ class NGPTrainer:
             torch.cuda.current_stream().wait_event(ev)
         self._set_lr()
         key = (k, bool(update_after), gt.data_ptr(), directions.data_ptr(), poses.data_ptr(), gt.shape, gt.dtype,
-               self.msets[k]["pre_ready"])
+               self.msets[k]["pre_ready"]) + self._exp_key()
+        self._expose_pending(k)
         if not self.dp:
             self._run_graph(key, lambda: self._graph_body(k, gt, directions, poses, update_after))
         else:
@@ -842,6 +943,8 @@ class NGPTrainer:
         self.cur = k
         self._bind(self.msets[k])
         self._pending = (1 - k, None)  # marched (and joined) inside the graph
+        if self.use_exposure:
+            self.msets[1 - k]["exp_key"] = self._exp_key()  # (a replay does not run _march)
         self.n_prefetched += 1
         self.global_step += 1
         if update_after:
@@ -917,7 +1020,8 @@ class NGPTrainer:
             torch.cuda.current_stream().wait_event(ev)
         self._set_lr()
         key = ("pair", k, gt.data_ptr(), directions.data_ptr(), poses.data_ptr(), gt.shape, gt.dtype,
-               self.msets[k]["pre_ready"])
+               self.msets[k]["pre_ready"]) + self._exp_key()
+        self._expose_pending(k)
 
         def body():
             self._graph_body(k, gt, directions, poses, False)
@@ -926,11 +1030,19 @@ class NGPTrainer:
         self.cur = 1 - k
         self._bind(self.msets[1 - k])
         self._pending = (k, None)  # the batch after both, marched inside the graph
+        if self.use_exposure:
+            self.msets[k]["exp_key"] = self.msets[1 - k]["exp_key"] = self._exp_key()
         self.n_prefetched += 2
         self.global_step += 1
         self._ran_ahead = True
-        self._pair_key = key[2:7]
+        self._pair_key = key[2:7] + self._exp_key()
         return self.out_loss
+
+    def _expose_pending(self, k):
+        """use_exposure: the batch marched ahead into set k took its exposures from the table of the call
+        that marched it; a call with another table fills them again (current stream, outside the graph)"""
+        if self.use_exposure and self.msets[k]["exp_key"] != self._exp_key():
+            self._expose(k, vren._stream())
 
     def _run_graph(self, key, body):
         """Replay the graph captured for `key` (capturing body() first if new;
@@ -1087,6 +1199,13 @@ class NGPTrainer:
             self._pose_state(poses)
             self._pose_args = (directions, poses)
         self._bind(self.msets[self.cur])
+        if self.use_exposure:
+            if src[0] == "sample":
+                self._expose_pending(self.cur)
+            else:
+                self.L.ngp_sample_exposure_rays(self.rays_a, self.batch_size, self._ray_exposure, self.cap,
+                                                self.sample_exposure, vren._stream())
+                self.msets[self.cur]["exp_key"] = None
         if rgb_gt is None:
             rgb_gt = self.rgb_gt
         self._ev("raygen_march", 1)
@@ -1136,7 +1255,15 @@ class NGPTrainer:
                 # recorded after round 1 -- the same dependencies -- ran 27 % slower: the graph's
                 # queue assignment follows the capture order, profiles/r06/ab/capture_order.txt)
                 marched = bool(fork())
-            self._field_indexed(s, self.eval_idx, self.eval_total2)
+            self._field_indexed(s, self.eval_idx, self.eval_total2, tone=False)
+            if self.use_exposure:
+                # exactly the samples the two rounds evaluated: round 1's rows (their first chunk_first
+                # samples: the chunk _rows_fwd admits), then round 2's list.  Both
+                # after round 2, so that round 1, the fork and round 2 are captured in the order above
+                # (the march then runs beside these as well)
+                L.ngp_tonemap_forward_rows(self.rgbs, self.cap, self.rays_a, self.rows_ne, self.n_rows_ne, R,
+                                           self.chunk_first, self.sample_exposure, self.tone16, self.ldr, s)
+                self._tonemap(s, self.eval_total2, self.eval_idx)
         elif self.chunk_first > 0:  # two rounds: first K samples per row, then the rest of unterminated rows
             K = self.chunk_first
             if self.eval1_K == K:  # built by this batch's march
@@ -1158,6 +1285,8 @@ class NGPTrainer:
             L.ngp_field_encode_mlp_act(self.xyzs, self.dirs, self.cap, self.n_samples, None, *self._field, self.enc,
                                        self.sigmas, self.rgbs, None, self.rgb_act, s)
             self._ev("hash_encode", 1)
+            if self.use_exposure:
+                self._tonemap(s, self.n_samples, None)
         self._ev("field_fwd", 1)
         if fork is not None and at == "fwd":
             marched = bool(fork())
@@ -1167,7 +1296,8 @@ class NGPTrainer:
             L.ngp_random_bg(self.bg_seed, self.dctr[1:], 0, bg, s)
         self._ev("composite_loss", 0)
         self._ev("composite", 0)
-        L.ngp_composite_loss(self.sigmas, self.rgbs, self.deltas, self.ts, self.rays_a, R, rgb_gt, bg, self.loss_type,
+        L.ngp_composite_loss(self.sigmas, self.ldr if self.use_exposure else self.rgbs, self.deltas, self.ts,
+                             self.rays_a, R, rgb_gt, bg, self.loss_type,
                              self.lambda_opacity, self.lambda_depth, self.lambda_distortion, self.scale, 1e-4,
                              self.dsig, self.drgb, self.out_rgb, self.out_op, self.out_depth, self.out_loss,
                              self.n_active, None, None, None, self.stats, s)
@@ -1200,12 +1330,28 @@ class NGPTrainer:
         if binned:
             seg_done = torch.cuda.Event()
             seg_done.record(cs)
+        if self.use_exposure:
+            # dL/dldr -> dL/dlog-radiance in place over the gradient-carrying samples, the tonemappers'
+            # gradient added into tone_grad; then the unit-exposure term (train.py:182-187).  After
+            # seg_done: the bucket plan (sample_idx only) may run beside these too
+            self._ev("tone_bwd", 0)
+            L.ngp_tonemap_backward_indexed(self.rgbs, self.sample_exposure, self.cap, self.n_active_total,
+                                           self.sample_idx, self.tone16, self.drgb, self.drgb, self.tone_grad,
+                                           self._tone_ws, s)
+            if self.unit_exposure_rgb is not None:
+                L.ngp_unit_exposure_term(self.tone16, self.unit_exposure_rgb, self.tone_grad, self.out_loss_unit, s)
+            self._ev("tone_bwd", 1)
         self._ev("mlp_bwd", 0)
         L.ngp_field_backward_mlp_act(self.dirs, self.cap, self.n_active_total, self.sample_idx, self.enc, self.cap,
                                      self.params16, self.dsig, self.drgb, self.denc, self.grad, self.rgb_act, s)
         self._ev("mlp_bwd", 1)
         if seg_done is not None:
             planned = plan(seg_done)
+        if self.use_exposure and apply_adam:
+            # the tonemappers' FusedAdam (one optimizer, one schedule with the field: train.py:139-151), on
+            # this stream after their last reader of the step; it clears tone_grad
+            L.ngp_adam_step_dev(self.tone_params, self.tone_grad, self.tone_exp_avg, self.tone_exp_avg_sq, self.tone16,
+                                HG.TONE_PARAMS, *self._adam_hp, 1, s)
         if self.optimize_ext:
             self._pose_backward(*self._pose_args, apply_adam)
         if fork is not None and at == "mlp":
@@ -1354,26 +1500,77 @@ class NGPTrainer:
         else:
             self.L.ngp_adam_step_dev(*args, s)
 
-    def _field_indexed(self, s, idx=None, total=None):
+    def _field_indexed(self, s, idx=None, total=None, tone=True):
         """Field forward (encode + MLPs in one launch) over the listed samples
         idx[:total] (default eval_idx[:eval_total]); the pair-major encoding
-        kept for the backward."""
+        kept for the backward.  use_exposure: followed by the tonemappers over
+        the same list (tone=False: the caller launches them)."""
         idx = self.eval_idx if idx is None else idx
         total = self.eval_total if total is None else total
         self._ev("hash_encode", 0)
         self.L.ngp_field_encode_mlp_act(self.xyzs, self.dirs, self.cap, total, idx, *self._field, self.enc, self.sigmas,
                                         self.rgbs, None, self.rgb_act, s)
         self._ev("hash_encode", 1)
+        if self.use_exposure and tone:
+            self._tonemap(s, total, idx)
+
+    # ------------------------------------------------- tonemappers' state (use_exposure)
+    def tone_state(self):
+        """{'tonemapper_net_{0,1,2}.params': (2048) f32}: the tonemappers in the reference
+        checkpoint's key layout (utils.tcnn_state_dict's entries for them), clones."""
+        if not self.use_exposure:
+            raise RuntimeError("tone_state needs a trainer built with use_exposure=True")
+        from utils import TONE_KEYS
+        n = HG.TONE_NET
+        return {k: self.tone_params[n * i:n * (i + 1)].detach().clone() for i, k in enumerate(TONE_KEYS)}
+
+    @torch.no_grad()
+    def load_tone_params(self, tone):
+        """Overwrite the tonemappers' fp32 master and fp16 shadow between steps: a flat (6144) tensor
+        ([T_0 | T_1 | T_2]) or tone_state()'s dict."""
+        if not self.use_exposure:
+            raise RuntimeError("load_tone_params needs a trainer built with use_exposure=True")
+        if isinstance(tone, dict):
+            from utils import TONE_KEYS
+            tone = torch.cat([tone[k].reshape(-1) for k in TONE_KEYS])
+        if tone.numel() != HG.TONE_PARAMS:
+            raise ValueError(f"the tonemappers hold {HG.TONE_PARAMS} values, got {tone.numel()}")
+        self.tone_params.copy_(tone.reshape(-1).to(self.tone_params))
+        self.tone16.copy_(self.tone_params.half())
+
+    @torch.no_grad()
+    def to_model(self):
+        """The trainer's state as the drop-in model: an NGP of the trainer's mode holding params, the
+        occupancy bitfield and, under use_exposure, tone_params (utils.tcnn_state_dict of it is the
+        reference's checkpoint, tonemapper_net_i.params included)."""
+        from models.networks import NGP
+        if self.use_exposure:
+            m = NGP(self.scale, 'None', False, use_exposure=True)
+        else:
+            m = NGP(self.scale, 'None' if self.use_raw_HDR else 'Sigmoid', self.use_raw_HDR)
+        m = m.to(self.dev)
+        m.params.copy_(self.full_params())
+        m.density_bitfield.copy_(self.density_bitfield)
+        if self.use_exposure:
+            m.tone_params.copy_(self.tone_params)
+        return m
 
     # ---------------------------------------------------- test-time render
     @torch.no_grad()
-    def render(self, rays_o, rays_d, T_threshold=1e-4, max_samples=MAX_SAMPLES, bg=0.0, output_radiance=False):
+    def render(self, rays_o, rays_d, T_threshold=1e-4, max_samples=MAX_SAMPLES, bg=0.0, output_radiance=False,
+               exposure=None):
         """__render_rays_test (models/rendering.py:162-253) on the native kernels.
         output_radiance: a raw-HDR trainer's relu radiance instead of the
-        training-time leaky_relu (networks.py:152-157); no effect on a sigmoid one."""
+        training-time leaky_relu (networks.py:152-157); no effect on a sigmoid one.
+        use_exposure: the samples' log radiance tonemapped at `exposure` (None:
+        1; one value; or one per ray (N_rays,) / (N_rays,1)), or with
+        output_radiance exp(clamp(x, 0, 20)) (networks.py:158-163)."""
         act = HG.RGB_RELU if self.use_raw_HDR and output_radiance else self.rgb_act
         N_rays = rays_o.shape[0]
         dev = self.dev
+        if exposure is not None and not self.use_exposure:
+            raise ValueError("exposure= needs a trainer built with use_exposure=True")
+        expo, n_expo = HG.tone_exposure(exposure, N_rays, rays_o.device) if self.use_exposure else (None, 0)
         _, hits_t, _ = vren.ray_aabb_intersect(rays_o, rays_d, self.center, self.half_size, 1)
         m = (hits_t[:, 0, 0] >= 0) & (hits_t[:, 0, 0] < NEAR_DISTANCE)
         hits_t[m, 0, 0] = NEAR_DISTANCE
@@ -1403,6 +1600,13 @@ class NGPTrainer:
             rgbs = torch.zeros(len(xyzs), 3, device=dev)
             sv, rv, _, _ = HG.field_forward(xyzs[valid].contiguous(), dirs[valid].contiguous(), self.grid,
                                             self.params16, save_enc=False, rgb_act=act)
+            if self.use_exposure and output_radiance:
+                rv = HG.tonemap_forward(rv, None, 0, None, HG.TONE_RADIANCE)
+            elif self.use_exposure and n_expo > 1:  # each ray's exposure on its Ns samples
+                e = expo[alive].repeat_interleave(Ns)[valid].contiguous()
+                rv = HG.tonemap_forward(rv, e, rv.shape[0], self.tone16)
+            elif self.use_exposure:
+                rv = HG.tonemap_forward(rv, expo, n_expo, self.tone16)
             sig[valid] = sv
             rgbs[valid] = rv
             vren.composite_test_fw(sig.view(-1, Ns), rgbs.view(-1, Ns, 3), deltas, ts, ht, alive, T_threshold, neff,

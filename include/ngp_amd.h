@@ -981,6 +981,64 @@ int ngp_tonemap_backward(const float* log_rad, const float* exposure, int64_t n_
                          const int64_t* n_dev, const void* tone_f16, const float* dL_drgbs, float* dL_dlog_rad,
                          float* grad_tone, void* workspace, void* stream);
 
+/* ---- exposure tonemappers in the training step -----------
+ * The fused step evaluates rows of rays_a (n_rays rows of (ray, start, N),
+ * i64) and compacted sample lists, and is given the exposure per ray; these
+ * are the forms of the kernels above it needs.  Every row they write holds the
+ * bits ngp_tonemap_forward / ngp_tonemap_backward give that row at the same
+ * exposure. */
+
+/* sample_exposure[start + k] = img_exposure[img_idxs[ray]], k < N, for every
+ * row (ray, start, N) of rays_a; img_idxs (n_rays, i64) is indexed by ray id,
+ * img_exposure holds n_img values.  The exposure itself is stored, not its
+ * log.  Slots no row owns keep their bits; nothing is written at or past n.
+ * A row whose ray is outside [0, n_rays), whose image is outside [0, n_img),
+ * whose start is negative or whose N <= 0 is skipped.  No atomics.  n_rays ==
+ * 0 or n == 0: no-op.  NGP_EINVAL, nothing launched: n_rays < 0, n < 0, n_img
+ * < 0, a null rays_a / img_idxs / img_exposure / sample_exposure. */
+int ngp_sample_exposure(const int64_t* rays_a, int64_t n_rays, const int64_t* img_idxs, const float* img_exposure,
+                        int64_t n_img, int64_t n, float* sample_exposure, void* stream);
+/* ... from one value per ray: sample_exposure[start + k] = ray_exposure[ray]
+ * (ray_exposure (n_rays), indexed by ray id).  NGP_EINVAL: n_rays < 0, n < 0,
+ * a null rays_a / ray_exposure / sample_exposure. */
+int ngp_sample_exposure_rays(const int64_t* rays_a, int64_t n_rays, const float* ray_exposure, int64_t n,
+                             float* sample_exposure, void* stream);
+/* NGP_TONE_LDR over the first min(N_r, first) samples of the rows r = rows[j],
+ * j < min(*n_rows_dev, n_rows), of rays_a (rows null: r = j; n_rows_dev null:
+ * n_rows; n_rows is also the number of rows of rays_a: the conventions of
+ * ngp_field_forward_first_pre_act), each sample at its own sample_exposure
+ * (n).  Every other row of rgbs (n,3) keeps its bits; rgbs may be log_rad (in
+ * place).  A listed row outside [0, n_rows) or with a negative start is
+ * skipped, and nothing at or past n is touched.  n == 0, n_rows == 0 or first
+ * == 0: no-op.  NGP_EINVAL, nothing launched: n < 0, n_rows < 0, first < 0, a
+ * null log_rad / rays_a / sample_exposure / tone_f16 / rgbs. */
+int ngp_tonemap_forward_rows(const float* log_rad, int64_t n, const int64_t* rays_a, const int32_t* rows,
+                             const int64_t* n_rows_dev, int64_t n_rows, int first, const float* sample_exposure,
+                             const void* tone_f16, float* rgbs, void* stream);
+/* ngp_tonemap_backward over the rows sample_idx[i], i < min(n, *n_dev) (the
+ * list ngp_field_backward_mlp_act walks; sample_idx null: the rows [0, min(n,
+ * *n_dev)), n_dev null: n), each at its own sample_exposure (n, indexed by
+ * sample).  dL_dlog_rad is written on the listed rows only (it may be
+ * dL_drgbs); rows off the list are neither read nor written; an index outside
+ * [0, n) is skipped.  dL/dtone is ADDED to grad_tone as ngp_tonemap_backward
+ * adds it: per-workgroup sums in `workspace`
+ * (ngp_tonemap_backward_indexed_workspace(n) bytes, 16-byte aligned), folded
+ * in workgroup order -- no atomics, two runs give the same bits.  A listed
+ * row whose dL_drgbs is 0 adds exactly nothing.  n == 0: no-op.  NGP_EINVAL,
+ * nothing launched: n < 0, a null log_rad / sample_exposure / tone_f16 /
+ * dL_drgbs / dL_dlog_rad / grad_tone / workspace, sample_idx without n_dev, a
+ * workspace not 16-byte aligned. */
+size_t ngp_tonemap_backward_indexed_workspace(int64_t n);
+int ngp_tonemap_backward_indexed(const float* log_rad, const float* sample_exposure, int64_t n, const int64_t* n_dev,
+                                 const int32_t* sample_idx, const void* tone_f16, const float* dL_drgbs,
+                                 float* dL_dlog_rad, float* grad_tone, void* workspace, void* stream);
+/* The unit-exposure term (train.py:182-187): y (3) = NGP_TONE_LDR of log
+ * radiance 0 at exposure 1 (ngp_tonemap_forward's bits), *out_loss = mean_c
+ * 0.5 (y_c - target)^2, and that mean's gradient ADDED to grad_tone
+ * (NGP_TONE_PARAMS f32).  One launch, no host sync.  NGP_EINVAL, nothing
+ * launched: a null tone_f16 / grad_tone / out_loss. */
+int ngp_unit_exposure_term(const void* tone_f16, float target, float* grad_tone, float* out_loss, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

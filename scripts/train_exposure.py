@@ -152,6 +152,84 @@ class ExposureLoop:
         return {e: sum(v) / len(v) for e, v in sorted(out.items())}
 
 
+class FusedLoop:
+    """The same data and hyper-parameters through the fused step, NGPTrainer(use_exposure=True,
+    unit_exposure_rgb=...): batches drawn on the device, the exposure one value per
+    training image (rays[:, 0, 3]), steady-state steps replayed as captured graphs."""
+
+    def __init__(self, data, batch=1024, lr=1e-2, seed=4, **kw):
+        from datasets.ray_utils import get_rays
+        from trainer import NGPTrainer
+        dev = data.directions.device
+        self.get_rays, self.data = get_rays, data
+        self.gt = data.train_rays[..., :3].contiguous()
+        self.table = data.train_rays[:, 0, 3].contiguous()
+        assert bool((data.train_rays[..., 3] == self.table[:, None]).all()), "one exposure per training image"
+        self.dirs, self.poses = data.directions.contiguous(), data.train_poses.contiguous()
+        self.tr = NGPTrainer(scale=data.scale, batch_size=batch, lr=lr, seed=seed, device=dev, erode=data.erode,
+                             use_exposure=True, unit_exposure_rgb=data.unit_exposure_rgb, **kw)
+        self.tr.mark_invisible_cells(data.K.to(dev), data.train_poses, data.img_wh)
+
+    def step(self, allow_pair=True):
+        """-> (the per-ray losses, None): on the device, not waited for; the unit-exposure term's value is
+        tr.out_loss_unit"""
+        return self.tr.train_step(self.gt, self.dirs, self.poses, allow_pair=allow_pair, exposure=self.table), None
+
+    def last_loss(self):
+        return float(self.tr.out_loss.sum() + self.tr.out_loss_unit[0])
+
+    @torch.no_grad()
+    def test_psnr(self):
+        """{exposure: mean PSNR over the test frames taken at it} (ExposureLoop.test_psnr on NGPTrainer.render)"""
+        d, tr, out = self.data, self.tr, {}
+        tr.drain()
+        for i in range(d.test_rays.shape[0]):
+            e = d.test_rays[i, 0, 3]
+            rays_o, rays_d = self.get_rays(d.directions, d.test_poses[i])
+            res = tr.render(rays_o.contiguous(), rays_d.contiguous(), bg=1.0 if tr.esf == 0 else 0.0, exposure=e.reshape(1))
+            mse = ((res['rgb'].clamp(0, 1) - d.test_rays[i, :, :3]) ** 2).mean()
+            out.setdefault(round(float(e), 6), []).append(float(-10 * torch.log10(mse)))
+        return {e: sum(v) / len(v) for e, v in sorted(out.items())}
+
+
+def fused_compare(data, a):
+    """--fused-compare N: ms/step of the drop-in loop and of the fused step on the same data, alternated
+    for N rounds of `--window` steps each (both warmed up past the occupancy warm-up first), and the
+    composited samples per step of each, the mean over each window (the work per step moves with the
+    model's state)."""
+    import time
+    loops = {"dropin": ExposureLoop(data, a.batch, a.lr, a.seed), "fused": FusedLoop(data, a.batch, a.lr, a.seed)}
+    for lp in loops.values():
+        for _ in range(a.steps):
+            lp.step()
+    tr = loops["fused"].tr
+    ms = {k: [] for k in loops}
+    samples = {k: [] for k in loops}
+    for _ in range(a.fused_compare):
+        for name, lp in loops.items():
+            torch.cuda.synchronize()
+            if name == "fused":
+                tr.reset_stats()
+            t0 = time.perf_counter()
+            vr = []  # (the drop-in loop's per-step counts, device tensors: read after the window)
+            for _ in range(a.window):
+                _, res = lp.step()
+                if res is not None:
+                    vr.append(res['vr_samples'])
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) / a.window * 1e3)
+            samples[name].append(tr.stat_totals()[1] / a.window if name == "fused"
+                                 else sum(float(v) for v in vr) / a.window)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    return {"rounds": a.fused_compare, "window": a.window, "warm_steps": a.steps,
+            "ms_per_step_dropin": round(med(ms["dropin"]), 4), "ms_per_step_fused": round(med(ms["fused"]), 4),
+            "ms_range_dropin": [round(min(ms["dropin"]), 4), round(max(ms["dropin"]), 4)],
+            "ms_range_fused": [round(min(ms["fused"]), 4), round(max(ms["fused"]), 4)],
+            "dropin_over_fused": round(med(ms["dropin"]) / med(ms["fused"]), 2),
+            "composited_per_step_dropin": round(med(samples["dropin"])),
+            "composited_per_step_fused": round(med(samples["fused"]))}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--root_dir", default=None, help="an HDR-NeRF scene folder; default: the synthetic multi-exposure scene")
@@ -165,18 +243,35 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=4)
     ap.add_argument("--torch-ops", action="store_true", help="the tonemappers restated in torch ops, not the kernels")
     ap.add_argument("--zero-exposure", action="store_true", help="ignore the exposure (the unconditioned model)")
+    ap.add_argument("--fused", action="store_true",
+                    help="train through the fused step, NGPTrainer(use_exposure=True, unit_exposure_rgb=...)")
+    ap.add_argument("--fused-compare", type=int, default=0, metavar="N",
+                    help="ms/step of the drop-in loop and of the fused step, alternated for N rounds after --steps "
+                         "warm-up steps of each")
+    ap.add_argument("--window", type=int, default=50, help="--fused-compare: steps per timed window")
     a = ap.parse_args(argv)
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     data = hdr_nerf_data(a.root_dir, a.downsample, a.scale, dev) if a.root_dir else \
         synthetic_data(a.res, a.images, 2, device=dev)
-    loop = ExposureLoop(data, a.batch, a.lr, a.seed, a.torch_ops, a.zero_exposure)
+    name = a.root_dir or f"synthetic multi-exposure {a.res}x{a.res}x{a.images}x{len(TRAIN_EXPOSURES)}"
+    if a.fused_compare:
+        print(json.dumps({"data": name, "batch": a.batch, **fused_compare(data, a)}))
+        return
+    if a.fused:
+        if a.torch_ops or a.zero_exposure:
+            raise SystemExit("--fused runs the kernels at the data's exposures: no --torch-ops, no --zero-exposure")
+        loop = FusedLoop(data, a.batch, a.lr, a.seed, num_epochs=max(1, a.steps // 1000))
+    else:
+        loop = ExposureLoop(data, a.batch, a.lr, a.seed, a.torch_ops, a.zero_exposure)
     loss = None
     for _ in range(a.steps):
         loss, _ = loop.step()
     torch.cuda.synchronize()
     psnr = loop.test_psnr()
-    print(json.dumps({"data": a.root_dir or f"synthetic multi-exposure {a.res}x{a.res}x{a.images}x{len(TRAIN_EXPOSURES)}",
+    if a.fused and loss is not None:
+        loss = torch.tensor(loop.last_loss())
+    print(json.dumps({"data": name, "loop": "fused" if a.fused else "dropin",
                       "steps": a.steps, "batch": a.batch, "tonemapper": "torch ops" if a.torch_ops else "kernels",
                       "zero_exposure": a.zero_exposure, "last_loss": round(float(loss.detach()), 5) if loss is not None else None,
                       "test_psnr_per_exposure": {str(e): round(v, 2) for e, v in psnr.items()},

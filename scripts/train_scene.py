@@ -38,6 +38,10 @@ def main(argv=None):
                     help="raw-HDR model (train.py:76-77 under --use_EXR): no colour activation, leaky_relu in "
                          "training, evaluated with output_radiance=True and without the [0,1] clamp; needs fp32 "
                          "ground truth")
+    ap.add_argument("--use_exposure", action="store_true",
+                    help="exposure-conditioned model on an HDR-NeRF folder (train.py:76-77 under --use_exposure; "
+                         "NGPTrainer(use_exposure=True)): the rays' 4th channel is the image's exposure, test frames are "
+                         "rendered at their own; --ckpt then also holds tonemapper_net_{0,1,2}.params")
     ap.add_argument("--optimize_ext", action="store_true",
                     help="refine the training cameras inside the fused step (opt.py:54; NGPTrainer(optimize_ext=True))")
     ap.add_argument("--pose_lr", type=float, default=1e-6, help="the reference hard-codes 1e-6 (train.py:149)")
@@ -55,18 +59,28 @@ def main(argv=None):
     if a.use_raw_HDR and not torch.as_tensor(train.rays).is_floating_point():
         raise SystemExit(f"--use_raw_HDR needs floating-point (fp32) ground truth; dataset {a.dataset!r} at {a.root} "
                          f"holds {torch.as_tensor(train.rays).dtype} pixels only")
-    gt = train.gt_f32().to(dev)  # float targets, as the reference's loss sees them
+    expo = {}
+    if a.use_exposure:
+        rays = torch.as_tensor(train.rays)
+        if rays.dim() != 3 or rays.shape[-1] != 4 or not bool((rays[..., 3] == rays[:, :1, 3]).all()):
+            raise SystemExit(f"--use_exposure needs rays (n_img, hw, 4) with one exposure per image in the 4th channel "
+                             f"(an HDR-NeRF folder); dataset {a.dataset!r} at {a.root} holds {tuple(rays.shape)}")
+        gt = rays[..., :3].float().contiguous().to(dev)
+        expo = {"exposure": rays[:, 0, 3].float().contiguous().to(dev)}  # one value per training image
+    else:
+        gt = train.gt_f32().to(dev)  # float targets, as the reference's loss sees them
     dirs, poses = train.directions.to(dev).contiguous(), train.poses.to(dev).contiguous()
     # erode for COLMAP scenes, as train.py:176-178 passes erode=dataset_name=='colmap'
     mode = dict(chunk_first=0, hash_backward="atomic") if a.exact else {}
     tr = NGPTrainer(scale=a.scale, batch_size=a.batch, device=dev, num_epochs=max(1, a.steps // 1000),
                     erode=a.dataset == "colmap", seed=a.seed, use_raw_HDR=a.use_raw_HDR,
-                    optimize_ext=a.optimize_ext, pose_lr=a.pose_lr, **mode)
+                    optimize_ext=a.optimize_ext, pose_lr=a.pose_lr, use_exposure=a.use_exposure,
+                    unit_exposure_rgb=getattr(train, "unit_exposure_rgb", None) if a.use_exposure else None, **mode)
     tr.mark_invisible_cells(train.K.to(dev), poses, train.img_wh)  # train.py:169-172
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for it in range(a.steps):
-        tr.train_step(gt, dirs, poses)
+        tr.train_step(gt, dirs, poses, **expo)
         if a.sync_every and (it + 1) % a.sync_every == 0:
             torch.cuda.synchronize()
             print(f"[train_scene] step {it + 1} ok, samples {int(tr.n_samples.item())}, occupied-cell count "
@@ -82,7 +96,8 @@ def main(argv=None):
         P = test.poses[i].to(dev)
         d = (tdirs @ P[:, :3].t()).contiguous()
         o = P[:, 3].expand_as(d).contiguous()
-        out = tr.render(o, d, bg=1.0 if tr.esf == 0 else 0.0, output_radiance=a.use_raw_HDR)
+        at = {"exposure": torch.as_tensor(test.rays[i])[0, 3].reshape(1).float().to(dev)} if a.use_exposure else {}
+        out = tr.render(o, d, bg=1.0 if tr.esf == 0 else 0.0, output_radiance=a.use_raw_HDR, **at)
         # sigmoid models are scored clamped to [0,1]; radiance is not clamped
         im.update(out["rgb"], test.rays[i].to(dev)[..., :3].float().contiguous(), clamp=not a.use_raw_HDR)
     scores = im.compute()
@@ -90,10 +105,12 @@ def main(argv=None):
         ck = {"params": tr.full_params().detach().cpu()}
         if tr.pose_refiner is not None:
             ck.update({k: v.cpu() for k, v in tr.pose_refiner.state_dict_reference().items()})
+        if a.use_exposure:
+            ck.update({k: v.cpu() for k, v in tr.tone_state().items()})
         torch.save(ck, a.ckpt)
     import vren
     res = {"dataset": a.dataset, "root": a.root, "steps": a.steps, "mode": "exact" if a.exact else "default",
-           "use_raw_HDR": bool(a.use_raw_HDR), "optimize_ext": bool(a.optimize_ext),
+           "use_raw_HDR": bool(a.use_raw_HDR), "optimize_ext": bool(a.optimize_ext), "use_exposure": bool(a.use_exposure),
            "guard_hits": int(vren.lib().ngp_guard_hits()),
            "train_rays_per_s": round(a.steps * a.batch / t_train, 1),
            "test_psnr": round(scores["mean_psnr"], 3), "test_ssim": round(scores["mean_ssim"], 4), "test_views": n}
