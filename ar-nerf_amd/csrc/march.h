@@ -26,6 +26,37 @@ __device__ __forceinline__ void aabb_t1t2(const float o[3], const float inv[3], 
     if (t1 > t2) { t1 = -1.0f; t2 = -1.0f; }
 }
 
+// ------------------------------------------------------ ray generation
+// (shared by the ray-generation kernels of march.hip and the insertion frame
+// opening of insert.hip)
+// datasets/ray_utils.py:45-70 (rays_d = dir_cam @ R^T, rays_o = c2w[:,3]) for
+// the gathered training batch (train.py:85-87), then the single-box AABB
+// test and the near clamp of models/rendering.py:29-31.
+__device__ __forceinline__ void gen_ray(const float* __restrict__ P, const float* __restrict__ dc,
+                                        const float* __restrict__ center, const float* __restrict__ half_size,
+                                        float near, float* __restrict__ ro, float* __restrict__ rd,
+                                        float* __restrict__ ht) {
+    const float d0 = dc[0], d1 = dc[1], d2 = dc[2];
+    // einsum 'n1c,nba->n1a' of rearranged c2w: d_i = sum_c dc_c * R[i][c],
+    // evaluated c-major like the batched matmul (fp32, no contraction).
+    float d[3], o[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        d[i] = d0 * P[4 * i + 0] + d1 * P[4 * i + 1] + d2 * P[4 * i + 2];
+        o[i] = P[4 * i + 3];
+    }
+    const float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
+    float t1, t2;
+    aabb_t1t2(o, inv, center, half_size, t1, t2);
+    float h0 = -1.0f, h1 = -1.0f;
+    if (t2 > 0) { h0 = fmaxf(t1, 0.0f); h1 = t2; }
+    if (h0 >= 0 && h0 < near) h0 = near;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { ro[i] = o[i]; rd[i] = d[i]; }
+    ht[0] = h0;
+    ht[1] = h1;
+}
+
 // --------------------------------------------------------- marching
 struct MarchParams {
     const uint8_t* bitfield;
@@ -353,3 +384,14 @@ static inline int march_attach_summary(MarchParams& p, const uint32_t* summary) 
 }
 // LDS for the summary and its dilation (both n_sum32 words)
 static inline size_t march_summary_lds(const MarchParams& p) { return (size_t)2 * p.n_sum32 * sizeof(uint32_t); }
+
+// ------------------------------------------- device-resident test render
+namespace ngp {
+// state (int64[NGP_RENDER_STATE_WORDS]) word indices (render.hip, insert.hip)
+enum : int { RS_ALIVE0 = 0, RS_ALIVE1 = 1, RS_SAMPLES = 2, RS_NS = 3, RS_ACTIVE = 4, RS_VALID = 5, RS_TOTAL = 6,
+             RS_ITERS = 7 };
+// render_march_kernel over at most n_rays alive rays (render.hip)
+void render_march_launch(const float* rays_o, const float* rays_d, float* hits_t, int64_t n_rays, const MarchParams& p,
+                         int parity, int64_t* state, const int32_t* alive, float* xyzs, float* dirs, float* deltas,
+                         float* ts, int32_t* n_eff, int32_t* sample_idx, hipStream_t s);
+}  // namespace ngp

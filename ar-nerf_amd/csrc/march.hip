@@ -60,34 +60,7 @@ __global__ void __launch_bounds__(64) ray_aabb_kernel(const float* __restrict__ 
     }
 }
 
-// datasets/ray_utils.py:45-70 (rays_d = dir_cam @ R^T, rays_o = c2w[:,3]) for
-// the gathered training batch (train.py:85-87), then the single-box AABB
-// test and the near clamp of models/rendering.py:29-31.
-__device__ __forceinline__ void gen_ray(const float* __restrict__ P, const float* __restrict__ dc,
-                                        const float* __restrict__ center, const float* __restrict__ half_size,
-                                        float near, float* __restrict__ ro, float* __restrict__ rd,
-                                        float* __restrict__ ht) {
-    const float d0 = dc[0], d1 = dc[1], d2 = dc[2];
-    // einsum 'n1c,nba->n1a' of rearranged c2w: d_i = sum_c dc_c * R[i][c],
-    // evaluated c-major like the batched matmul (fp32, no contraction).
-    float d[3], o[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        d[i] = d0 * P[4 * i + 0] + d1 * P[4 * i + 1] + d2 * P[4 * i + 2];
-        o[i] = P[4 * i + 3];
-    }
-    const float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
-    float t1, t2;
-    aabb_t1t2(o, inv, center, half_size, t1, t2);
-    float h0 = -1.0f, h1 = -1.0f;
-    if (t2 > 0) { h0 = fmaxf(t1, 0.0f); h1 = t2; }
-    if (h0 >= 0 && h0 < near) h0 = near;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { ro[i] = o[i]; rd[i] = d[i]; }
-    ht[0] = h0;
-    ht[1] = h1;
-}
-
+// (gen_ray: march.h)
 __global__ void __launch_bounds__(256) raygen_aabb_kernel(
     const float* __restrict__ directions, const float* __restrict__ poses,
     const int64_t* __restrict__ img_idx, const int64_t* __restrict__ pix_idx, int64_t n_rays,

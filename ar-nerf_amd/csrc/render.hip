@@ -24,9 +24,7 @@
 
 namespace ngp {
 
-// state (int64[NGP_RENDER_STATE_WORDS]) word indices
-enum : int { RS_ALIVE0 = 0, RS_ALIVE1 = 1, RS_SAMPLES = 2, RS_NS = 3, RS_ACTIVE = 4, RS_VALID = 5, RS_TOTAL = 6,
-             RS_ITERS = 7 };
+// (state word indices RS_*: march.h)
 
 __global__ void __launch_bounds__(256) render_begin_kernel(int64_t n_rays, int64_t* __restrict__ state,
                                                            int32_t* __restrict__ alive0, float* __restrict__ opacity,
@@ -450,6 +448,23 @@ using namespace ngp;
 
 static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
+// The march of one loop iteration over the alive rays (at most n_rays: the
+// grid is an upper bound, the kernel strides over state[parity]); shared by
+// ngp_render_test_march and ngp_render_test_march_n (insert.hip).
+void ngp::render_march_launch(const float* rays_o, const float* rays_d, float* hits_t, int64_t n_rays,
+                              const MarchParams& p, int parity, int64_t* state, const int32_t* alive, float* xyzs,
+                              float* dirs, float* deltas, float* ts, int32_t* n_eff, int32_t* sample_idx,
+                              hipStream_t s) {
+    const unsigned blocks = std::min(nblk(n_rays, 256), 2048u);
+    const int wave_ns = WAVE_NS;
+    if (march_simple(p))
+        render_march_kernel<true><<<blocks, 256, march_summary_lds(p), s>>>(
+            rays_o, rays_d, hits_t, p, state, parity, alive, xyzs, dirs, deltas, ts, n_eff, sample_idx, wave_ns);
+    else
+        render_march_kernel<false><<<blocks, 256, march_summary_lds(p), s>>>(
+            rays_o, rays_d, hits_t, p, state, parity, alive, xyzs, dirs, deltas, ts, n_eff, sample_idx, wave_ns);
+}
+
 extern "C" {
 
 int64_t ngp_render_test_capacity(int64_t n_rays, int min_samples) {
@@ -484,14 +499,8 @@ int ngp_render_test_march(const float* rays_o, const float* rays_d, float* hits_
     render_iter_kernel<<<1, 64, 0, s>>>(state, parity, n_rays, min_samples, sample_budget);
     if (n_rays == 0) return ngp_launch_status();
     NGP_CHECK_ARG(rays_o && rays_d && hits_t && alive && xyzs && dirs && deltas && ts && n_eff && sample_idx);
-    const unsigned blocks = std::min(nblk(n_rays, 256), 2048u);
-    const int wave_ns = WAVE_NS;
-    if (march_simple(p))
-        render_march_kernel<true><<<blocks, 256, march_summary_lds(p), s>>>(
-            rays_o, rays_d, hits_t, p, state, parity, alive, xyzs, dirs, deltas, ts, n_eff, sample_idx, wave_ns);
-    else
-        render_march_kernel<false><<<blocks, 256, march_summary_lds(p), s>>>(
-            rays_o, rays_d, hits_t, p, state, parity, alive, xyzs, dirs, deltas, ts, n_eff, sample_idx, wave_ns);
+    render_march_launch(rays_o, rays_d, hits_t, n_rays, p, parity, state, alive, xyzs, dirs, deltas, ts, n_eff,
+                        sample_idx, s);
     return ngp_launch_status();
 }
 

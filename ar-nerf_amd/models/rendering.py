@@ -85,13 +85,18 @@ def _test_renderer(model, n_rays, esf, T_threshold, max_samples, rgb_act=0, tone
                              tone16=None if t16 is None else t16.clone(), tone_mode=tone_mode)
         rr._src = rr._tone_src = None
         cache[key] = rr
+    _refresh_shadows(rr, p16, t16)
+    return rr
+
+
+def _refresh_shadows(rr, p16, t16):
+    """A cached renderer's own copies of the model's fp16 shadows, refreshed when the model made new ones."""
     if rr._src is not p16:  # parameters changed since the last frame: refresh the renderer's copy
         rr.params16.copy_(p16)
         rr._src = p16
     if t16 is not None and rr._tone_src is not t16:  # (the tone shadow likewise)
         rr.tone16.copy_(t16)
         rr._tone_src = t16
-    return rr
 
 
 def _frame_exposure(kwargs):
@@ -179,6 +184,56 @@ def __render_rays_test(model, rays_o, rays_d, hits_t, **kwargs):
         rgb_bg = _background(kwargs, rays_d, torch.zeros(3, device=device))
         results['rgb'] += rgb_bg * (1 - opacity)[:, None]
     return results
+
+
+@torch.no_grad()
+def render_insert(model, c2w, directions, H, W, rect, obj_rgb, obj_depth, **kwargs):
+    """The body of the insertion app's Insertor.render_insert_object
+    (insert/main.py:632-660) in one call: the rays of the screen rectangle
+    rect = (hs, ws, hl, wl) of the H x W camera `directions` (H*W,3) at the
+    (3,4) pose c2w, render(test_time=True, IM_bkg=obj_rgb[hs:hl, ws:wl],
+    mesh_depth_map=obj_depth[hs:hl, ws:wl]) and the write into the persistent
+    last_rgb / last_depth canvases, plus pts = rays_o + rays_d * depth
+    (main.py:429).  obj_rgb (H,W,3) / obj_depth (H,W): the shaded object and
+    its depth over the whole frame.  kwargs as the app's render takes them:
+    T_threshold, max_samples, exp_step_factor, exposure (None or one value),
+    output_radiance.
+
+    One renderer.InsertRenderer is cached on the model per (H, W, camera,
+    loop settings, bitfield, modes) and serves every rectangle without
+    re-capture.  Returns views of its canvases: rgb (H,W,3), depth (H,W), pts
+    (H,W,3) -- pixels outside the rectangle keep the last frame's values -- and
+    total_samples."""
+    import renderer as RD
+    esf = kwargs.get('exp_step_factor', 0.)
+    T_threshold, max_samples = kwargs.get('T_threshold', 1e-4), kwargs.get('max_samples', MAX_SAMPLES)
+    radiance = kwargs.get('output_radiance', False)
+    rgb_act = int(model.rgb_mode(radiance))
+    tone_mode = model.tone_mode(radiance)
+    directions = directions.reshape(-1, 3)
+    cache = model.__dict__.setdefault('_insert_renderers', {})
+    key = (int(H), int(W), directions.data_ptr(), float(esf), float(T_threshold), int(max_samples),
+           model.density_bitfield.data_ptr(), rgb_act, tone_mode)
+    rr = cache.get(key)
+    p16 = model._shadow.get()
+    t16 = model._tone_shadow.get() if tone_mode is not None else None
+    if rr is None:
+        if len(cache) >= 4:
+            cache.clear()
+        rr = RD.InsertRenderer(H, W, directions, model.center, model.half_size, model.grid, p16.clone(),
+                               model.density_bitfield, model.cascades, model.scale, model.grid_size,
+                               exp_step_factor=esf, T_threshold=T_threshold, max_samples=max_samples,
+                               iters_per_graph=16, iters_tail=8, rgb_act=rgb_act,
+                               tone16=None if t16 is None else t16.clone(), tone_mode=tone_mode)
+        rr._src = rr._tone_src = None
+        cache[key] = rr
+    _refresh_shadows(rr, p16, t16)
+    if tone_mode is not None:
+        uniform, exposure = _frame_exposure(kwargs)
+        if not uniform:
+            raise ValueError("render_insert takes one exposure per frame")
+        rr.set_exposure(exposure)
+    return rr.render_rect(c2w, rect, obj_rgb, obj_depth)
 
 
 def __render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):

@@ -19,6 +19,12 @@ only while the device says the loop is still running -- one host sync per
 graph; iterations after the loop ends are no-ops (early exits).
 Results (opacity, depth, rgb, total_samples) equal the host loop's bit for
 bit: tests/test_renderer_gpu.py.
+
+InsertRenderer is the same loop for the insertion app's frames:
+the ray count comes from device memory (ngp_insert_frame_begin,
+ngp_render_test_march_n, ngp_insert_frame_finish), so one renderer sized for
+the frame renders any screen rectangle without re-capture:
+tests/test_insert_gpu.py.
 """
 from __future__ import annotations
 
@@ -101,18 +107,23 @@ class TestRenderer:
         self.summary = torch.zeros(2 * ((density_bitfield.numel() + 255) // 256), dtype=torch.int32, device=dev)
         self.n_valid = self.state[RS_VALID:]  # (the valid-sample list's length, where the field kernel reads it)
         self._graphs = {}
+        self.n_captures = 0  # graphs captured so far (two per renderer: A and B)
         self.last_iterations = 0
         # full-frame camera (render_pose)
         self._dirs = None
 
     # ------------------------------------------------------------ pieces
+    def _march(self, par):
+        """Loop test, N_samples and the march of one iteration (rendering.py:186-203)."""
+        vren.kernels().ngp_render_test_march(
+            self.rays_o, self.rays_d, self.hits_t, self.n_rays, self.bitfield, self.cascades, self.grid_size,
+            self.scale, self.esf, MAX_SAMPLES, self.min_samples, self.max_samples, par, self.state, self.alive[par],
+            self.summary, self.xyzs, self.dirs, self.deltas, self.ts, self.n_eff, self.sample_idx, vren._stream())
+
     def _iteration(self, k):
         """One loop iteration (rendering.py:186-236) on the current stream."""
         K, s, par = vren.kernels(), vren._stream(), k & 1
-        K.ngp_render_test_march(self.rays_o, self.rays_d, self.hits_t, self.n_rays, self.bitfield, self.cascades,
-                                self.grid_size, self.scale, self.esf, MAX_SAMPLES, self.min_samples, self.max_samples,
-                                par, self.state, self.alive[par], self.summary, self.xyzs, self.dirs, self.deltas,
-                                self.ts, self.n_eff, self.sample_idx, s)
+        self._march(par)
         # model(xyzs[valid], dirs[valid]) (rendering.py:204-218): NGP.forward over the list
         # (encode + MLPs in one launch; no encoding kept: nothing goes backward)
         K.ngp_field_encode_mlp_act(self.xyzs, self.dirs, self.cap, self.n_valid, self.sample_idx, self.grid.desc,
@@ -141,6 +152,10 @@ class TestRenderer:
         if not self.use_graphs:
             self._run(first)
             return
+        self._graph(first).replay()
+
+    def _graph(self, first):
+        """Graph A (first) or B, captured on first use (capture does not execute)."""
         g = self._graphs.get(first)
         if g is None:
             g = torch.cuda.CUDAGraph()
@@ -148,8 +163,8 @@ class TestRenderer:
             with vren.graph_capture(g):
                 self._run(first)
             self._graphs[first] = g
-            # capture does not execute: run the frame opening for real below
-        g.replay()
+            self.n_captures += 1
+        return g
 
     # --------------------------------------------------------------- API
     @torch.no_grad()
@@ -218,12 +233,146 @@ class TestRenderer:
         return self.render_loaded()
 
 
-def for_model(model, n_rays, output_radiance=False, **kwargs):
-    """TestRenderer over a models.networks.NGP (its fp16 shadow and bitfield;
-    the model's colour mode, relu for a raw-HDR model with output_radiance)."""
+def _model_kwargs(model, output_radiance, kwargs):
+    """The model's colour mode (relu for a raw-HDR model with output_radiance) and,
+    for an exposure model, its tonemap mode and tone shadow, as renderer kwargs."""
     kwargs.setdefault('rgb_act', model.rgb_mode(output_radiance))
     if getattr(model, 'use_exposure', False):  # (its tone shadow in place: refresh with rr.tone16.copy_)
         kwargs.setdefault('tone_mode', model.tone_mode(output_radiance))
         kwargs.setdefault('tone16', model._tone_shadow.get())
+    return kwargs
+
+
+def for_model(model, n_rays, output_radiance=False, **kwargs):
+    """TestRenderer over a models.networks.NGP (its fp16 shadow and bitfield;
+    the model's colour mode, relu for a raw-HDR model with output_radiance)."""
+    kwargs = _model_kwargs(model, output_radiance, kwargs)
     return TestRenderer(n_rays, model.grid, model._shadow.get(), model.density_bitfield, model.cascades,
                         model.scale, model.grid_size, **kwargs)
+
+
+HEADER_WORDS = C["NGP_INSERT_HEADER_WORDS"]
+
+
+class InsertRenderer(TestRenderer):
+    """The insertion app's per-frame render (insert/main.py:620-684,
+    Insertor.render_insert_object) for one camera: a screen rectangle of the
+    H x W frame, every ray ended at the virtual object's surface
+    (mesh_depth_map, rendering.py:38-44), the shaded object blended in behind
+    what is left (IM_bkg, rendering.py:245-250), scattered into the persistent
+    canvases frame_rgb / frame_depth (main.py:652-654) with the surface points
+    frame_pts = rays_o + rays_d * depth (main.py:429).
+
+    The rectangle is a device value: buffers and graphs are
+    sized for the whole frame and captured once, whatever rectangles follow
+    (n_captures stays at 2); a rectangle's pixels equal those of a TestRenderer
+    built for its ray count, bit for bit.
+
+    directions (H*W,3); center / half_size: the model's box.  `buffers` may
+    give preallocated obj_rgb (H*W,3), obj_depth (H*W), frame_rgb (H*W,3),
+    frame_depth (H*W), frame_pts (H*W,3) tensors (contiguous fp32, e.g. views
+    of an application's own allocations)."""
+
+    def __init__(self, H, W, directions, center, half_size, grid, params16, density_bitfield, cascades, scale,
+                 grid_size=128, buffers=None, **kwargs):
+        H, W = int(H), int(W)
+        if H < 1 or W < 1 or H * W >= 2 ** 31:
+            raise ValueError(f"bad frame size {H} x {W}")
+        super().__init__(H * W, grid, params16, density_bitfield, cascades, scale, grid_size, **kwargs)
+        self.H, self.W = H, W
+        dev, n = params16.device, H * W
+        vren._check("directions", directions, torch.float32)
+        if directions.numel() != 3 * n:
+            raise ValueError(f"directions must hold H*W = {n} rows of 3, got {tuple(directions.shape)}")
+        self._dirs = directions
+        self._center, self._half = center.float().contiguous(), half_size.float().contiguous()
+        self._pose = torch.zeros(3, 4, dtype=torch.float32, device=dev)
+        buffers = dict(buffers or {})
+        for name, cols in (("obj_rgb", 3), ("obj_depth", 1), ("frame_rgb", 3), ("frame_depth", 1), ("frame_pts", 3)):
+            t = buffers.pop(name, None)
+            if t is None:
+                t = torch.zeros((n, 3) if cols == 3 else (n,), dtype=torch.float32, device=dev)
+            vren._check(name, t, torch.float32)
+            if t.numel() != n * cols:
+                raise ValueError(f"{name} must hold {n * cols} values, got {tuple(t.shape)}")
+            setattr(self, name, t)
+        if buffers:
+            raise ValueError(f"unknown buffers {sorted(buffers)}")
+        self.rect = torch.zeros(4, dtype=torch.int32, device=dev)  # (hs, ws, hl, wl): graph A reads it, the kernel clamps it
+        self._rect_host = torch.zeros(4, dtype=torch.int32).pin_memory()
+        self.header = torch.zeros(HEADER_WORDS, dtype=torch.int64, device=dev)
+
+    # ------------------------------------------------------------ pieces
+    def _begin(self):
+        vren.kernels().ngp_insert_frame_begin(
+            self.rect, self.H, self.W, self._dirs, self._pose, self._center, self._half, NEAR_DISTANCE,
+            self.obj_depth, self.rays_o, self.rays_d, self.hits_t, self.state, self.alive[0], self.opacity,
+            self.depth, self.rgb, self.header, vren._stream())
+        vren.bitfield_summary(self.bitfield, self.grid_size, out=self.summary)
+
+    def _march(self, par):
+        vren.kernels().ngp_render_test_march_n(
+            self.rays_o, self.rays_d, self.hits_t, self.header, self.n_rays, self.bitfield, self.cascades,
+            self.grid_size, self.scale, self.esf, MAX_SAMPLES, self.min_samples, self.max_samples, par, self.state,
+            self.alive[par], self.summary, self.xyzs, self.dirs, self.deltas, self.ts, self.n_eff, self.sample_idx,
+            vren._stream())
+
+    # --------------------------------------------------------------- API
+    def _set_rect(self, rect):
+        if isinstance(rect, torch.Tensor):
+            if rect.dtype != torch.int32 or rect.numel() != 4 or not rect.is_cuda:
+                raise ValueError("rect must be four ints or a device int32[4] tensor (hs, ws, hl, wl)")
+            if rect.data_ptr() != self.rect.data_ptr():
+                self.rect.copy_(rect.reshape(4))  # (device to device: no host wait)
+            return
+        hs, ws, hl, wl = (int(v) for v in rect)
+        if not (0 <= hs <= hl <= self.H and 0 <= ws <= wl <= self.W):
+            raise ValueError(f"rect (hs, ws, hl, wl) = {(hs, ws, hl, wl)} does not lie in the {self.H} x {self.W} frame")
+        # (the previous frame ended in a host sync after its copy: the pinned words are free again)
+        self._rect_host.copy_(torch.tensor([hs, ws, hl, wl], dtype=torch.int32))
+        self.rect.copy_(self._rect_host, non_blocking=True)
+
+    @torch.no_grad()
+    def render_rect(self, c2w, rect, obj_rgb=None, obj_depth=None):
+        """One insertion frame: rows hs..hl, columns ws..wl (rect = (hs, ws, hl, wl): four ints, checked here,
+        or a device int32[4] tensor, clamped to the frame by the kernel) seen from the (3,4) pose c2w, with the
+        whole-frame object images obj_rgb (H,W,3) / obj_depth (H,W) (None: what the renderer's buffers hold).
+        Returns views of the canvases (pixels outside the rectangle keep the last frame's values) and
+        total_samples; copy them to keep them past the next frame."""
+        self._pose.copy_(c2w.reshape(3, 4))
+        self._set_rect(rect)
+        if obj_rgb is not None:
+            self.obj_rgb.copy_(obj_rgb.reshape(self.obj_rgb.shape))
+        if obj_depth is not None:
+            self.obj_depth.copy_(obj_depth.reshape(self.obj_depth.shape))
+        if self.use_graphs and not self._graphs:  # both graphs now: no later frame, whatever its rectangle, captures
+            self._graph(True)
+            self._graph(False)
+        self._launch(True)
+        while int(self.state[RS_ACTIVE].item()):
+            self._launch(False)
+        self.last_iterations = int(self.state[RS_ITERS].item())
+        # (the closing launch runs outside the captured graphs, like TestRenderer's finish)
+        vren.kernels().ngp_insert_frame_finish(
+            self.header, self.H, self.W, self.opacity, self.depth, self.rgb, self.rays_o, self.rays_d, self.obj_rgb,
+            self.frame_rgb, self.frame_depth, self.frame_pts, vren._stream())
+        H, W = self.H, self.W
+        return {"rgb": self.frame_rgb.view(H, W, 3), "depth": self.frame_depth.view(H, W),
+                "pts": self.frame_pts.view(H, W, 3), "total_samples": self.state[RS_TOTAL]}
+
+    def render_frame(self, c2w, obj_rgb=None, obj_depth=None):
+        """render_rect over the whole screen (the app's frame after a camera move)."""
+        return self.render_rect(c2w, (0, 0, self.H, self.W), obj_rgb, obj_depth)
+
+    def render_loaded(self, bg_sh=None):
+        raise RuntimeError("InsertRenderer renders rectangles of its camera: use render_rect / render_frame")
+
+    def set_camera(self, directions, center, half_size):
+        raise RuntimeError("InsertRenderer is built for its camera")
+
+
+def insert_for_model(model, H, W, directions, output_radiance=False, **kwargs):
+    """InsertRenderer over a models.networks.NGP and its box, as for_model."""
+    kwargs = _model_kwargs(model, output_radiance, kwargs)
+    return InsertRenderer(H, W, directions, model.center, model.half_size, model.grid, model._shadow.get(),
+                          model.density_bitfield, model.cascades, model.scale, model.grid_size, **kwargs)

@@ -281,6 +281,56 @@ int ngp_render_test_composite(const float* sigmas, const float* rgbs, const floa
 /* rgb += bg_rgb (host float[3]) * (1 - opacity) (rendering.py:240-251) */
 int ngp_render_test_finish(const float* opacity, int64_t n_rays, const float* bg_rgb, float* rgb, void* stream);
 
+/* ---- insertion frames -----------------------------------
+ * The insertion app's per-frame call (insert/main.py:620-684): the screen
+ * rectangle rows hs..hl, columns ws..wl of an H x W frame is rendered with
+ * every ray ended at the virtual object's surface (mesh_depth_map,
+ * models/rendering.py:38-44) and the shaded object blended in behind what is
+ * left (IM_bkg, rendering.py:245-250), and scattered into persistent canvases
+ * (main.py:652-654).  The rectangle, and with it the ray count n, is a DEVICE
+ * value, so one set of buffers and captured graphs sized for the whole frame
+ * renders any rectangle, bit for bit as a loop built for its n rays.
+ * header: int64[NGP_INSERT_HEADER_WORDS] = [0] n, [1..4] the clamped
+ * (hs, ws, hl, wl), [5] H, [6] W, [7] 0; separate from `state`.
+ * Ray i < n is pixel p = (hs + i / w) * W + ws + i % w, w = wl - ws. */
+#define NGP_INSERT_HEADER_WORDS 8
+/* Frame opening.  rect: device int32[4] = (hs, ws, hl, wl), clamped here to
+ * [0,H] x [0,W]; inverted or empty gives n = 0.  For i < n: the ray of pixel p
+ * as ngp_raygen_aabb generates it (directions (H*W,3), one (3,4) pose, box,
+ * near clamp), then `if (obj_depth[p] >= 1e-6f) t2 = max(min(t2, obj_depth[p]),
+ * t1)` (a ray that misses the box keeps -1), into rows i of rays_o / rays_d
+ * (.,3) and hits_t (.,2); and the work of ngp_render_test_begin for n rays
+ * (state, alive0 = arange(n), opacity / depth / rgb rows zeroed).  Rows >= n
+ * of every buffer keep their bits.  All per-ray buffers hold H*W rows;
+ * H, W >= 1, H*W < 2^31. */
+int ngp_insert_frame_begin(const int32_t* rect, int64_t H, int64_t W, const float* directions, const float* pose,
+                           const float* center, const float* half_size, float near_distance, const float* obj_depth,
+                           float* rays_o, float* rays_d, float* hits_t, int64_t* state, int32_t* alive0, float* opacity,
+                           float* depth, float* rgb, int64_t* header, void* stream);
+/* ngp_render_test_march with the frame's ray count read from *n_rays_dev
+ * (header[0]) for the iteration rule N_samples = max(min(N_rays // N_alive,
+ * 64), min_samples); n_rays_cap (>= *n_rays_dev: the rows of the buffers)
+ * sizes the launch and the argument checks.  ngp_render_test_composite,
+ * ngp_field_encode_mlp_act and ngp_tonemap_forward take n_rays_cap as they
+ * are: their grids are upper bounds, the kernels stride over the counts in
+ * `state`.  Slots: N_alive * N_samples <= n * min_samples <= n_rays_cap *
+ * min_samples, so ngp_render_test_capacity(n_rays_cap, min_samples) bounds
+ * the slots of every rectangle. */
+int ngp_render_test_march_n(const float* rays_o, const float* rays_d, float* hits_t, const int64_t* n_rays_dev,
+                            int64_t n_rays_cap, const uint8_t* bitfield, int cascades, int grid_size, float scale,
+                            float exp_step_factor, int max_samples, int min_samples, int64_t sample_budget, int parity,
+                            int64_t* state, const int32_t* alive, const uint32_t* occ_summary, float* xyzs,
+                            float* dirs, float* deltas, float* ts, int32_t* n_eff, int32_t* sample_idx, void* stream);
+/* Frame closing, n and the rectangle from `header`: for i < n at pixel p,
+ * frame_rgb[p] = rgb[i] + obj_rgb[p] * (1 - opacity[i]), frame_depth[p] =
+ * depth[i] and, frame_pts non-null, frame_pts[p] = rays_o[i] + rays_d[i] *
+ * depth[i] (main.py:429).  obj_rgb, frame_rgb, frame_pts (H*W,3), frame_depth
+ * (H*W).  Pixels outside the rectangle keep their bits; one writer per pixel,
+ * no atomics. */
+int ngp_insert_frame_finish(const int64_t* header, int64_t H, int64_t W, const float* opacity, const float* depth,
+                            const float* rgb, const float* rays_o, const float* rays_d, const float* obj_rgb,
+                            float* frame_rgb, float* frame_depth, float* frame_pts, void* stream);
+
 /* ------------------------------------------------------- light probes */
 /* The insertion app's light probes (insert/main.py:306-407): R rays from each
  * of P scene points, the global light blended in behind them as an SH9
