@@ -29,19 +29,27 @@ void ngp_timing_mark(int id, int end, hipStream_t s) {
                                   ((int64_t)id * g_per + i) * 2 + (end ? 1 : 0));
 }
 
-// device probes: every translation unit registers the setter of its copy of
-// the control symbol (common.h) at load time
-static void (*g_probe_setters[16])(const ProbeCtl&);
+// Every translation unit registers, at load time, the setter of its copy of the
+// probe control symbol and the reader of its guard counter (common.h).  The
+// tables hold NGP_MAX_TUS entries; a registration past that is not dropped
+// silently: ngp_guard_hits() then reads as unreadable (~0) and ngp_probe_set fails.
+constexpr int NGP_MAX_TUS = 32;
+static bool g_register_overflow = false;  // (constant-initialised: set during other units' dynamic initialisation)
+
+// device probes
+static void (*g_probe_setters[NGP_MAX_TUS])(const ProbeCtl&);
 static int g_n_probe_setters = 0;
 void ngp_probe_register(void (*set)(const ProbeCtl&)) {
-    if (g_n_probe_setters < 16) g_probe_setters[g_n_probe_setters++] = set;
+    if (g_n_probe_setters < NGP_MAX_TUS) g_probe_setters[g_n_probe_setters++] = set;
+    else g_register_overflow = true;
 }
 
 // capacity guards: each translation unit's counter reader (common.h)
-static unsigned long long (*g_guard_getters[16])(int);
+static unsigned long long (*g_guard_getters[NGP_MAX_TUS])(int);
 static int g_n_guard_getters = 0;
 void ngp_guard_register(unsigned long long (*get)(int)) {
-    if (g_n_guard_getters < 16) g_guard_getters[g_n_guard_getters++] = get;
+    if (g_n_guard_getters < NGP_MAX_TUS) g_guard_getters[g_n_guard_getters++] = get;
+    else g_register_overflow = true;
 }
 
 // a kernel whose only purpose is its name in a dispatch trace (ngp_trace_marker)
@@ -81,6 +89,7 @@ int ngp_timing_set(uint64_t* stamps, const int64_t* step_dev, int64_t ring, int 
 
 int ngp_probe_set(uint64_t* buf, const int64_t* step_dev, int64_t ring) {
     if (buf && (!step_dev || ring < 1)) return NGP_EINVAL;
+    if (g_register_overflow) return NGP_EINVAL;
     const ProbeCtl c{(unsigned long long*)buf, buf ? step_dev : nullptr, buf ? ring : 0};
     for (int i = 0; i < g_n_probe_setters; ++i) g_probe_setters[i](c);
     const hipError_t e = hipDeviceSynchronize();
@@ -90,6 +99,7 @@ int ngp_probe_set(uint64_t* buf, const int64_t* step_dev, int64_t ring) {
 int ngp_probe_count(void) { return NGP_P_COUNT; }
 
 unsigned long long ngp_guard_hits(void) {
+    if (g_register_overflow) return ~0ull;  // a translation unit's counter is not in the table: unreadable
     unsigned long long s = 0;
     for (int i = 0; i < g_n_guard_getters; ++i) {
         const unsigned long long v = g_guard_getters[i](0);

@@ -19,28 +19,13 @@
 //   render_iter_n_kernel        render_iter_kernel with N_rays = header[0]
 //   insert_frame_finish_kernel  IM_bkg blend + scatter into the canvases + pts
 #pragma clang fp contract(off)
+#include "insert.h"
 #include "march.h"
 
 namespace ngp {
 
 // header (int64[NGP_INSERT_HEADER_WORDS]) word indices
 enum : int { IH_N = 0, IH_HS = 1, IH_WS = 2, IH_HL = 3, IH_WL = 4, IH_H = 5, IH_W = 6 };
-
-struct Rect {
-    int64_t hs, ws, hl, wl, n;
-};
-
-// (hs, ws, hl, wl) clamped to [0,H] x [0,W]; inverted or empty: n = 0
-__device__ __forceinline__ Rect clamp_rect(int64_t hs, int64_t ws, int64_t hl, int64_t wl, int64_t H, int64_t W) {
-    Rect r;
-    r.hs = hs < 0 ? 0 : (hs > H ? H : hs);
-    r.hl = hl < 0 ? 0 : (hl > H ? H : hl);
-    r.ws = ws < 0 ? 0 : (ws > W ? W : ws);
-    r.wl = wl < 0 ? 0 : (wl > W ? W : wl);
-    const int64_t h = r.hl - r.hs, w = r.wl - r.ws;
-    r.n = (h > 0 && w > 0) ? h * w : 0;
-    return r;
-}
 
 __global__ void __launch_bounds__(256) insert_frame_begin_kernel(
     const int32_t* __restrict__ rect, int64_t H, int64_t W, const float* __restrict__ directions,

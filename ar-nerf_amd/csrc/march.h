@@ -27,24 +27,29 @@ __device__ __forceinline__ void aabb_t1t2(const float o[3], const float inv[3], 
 }
 
 // ------------------------------------------------------ ray generation
-// (shared by the ray-generation kernels of march.hip and the insertion frame
-// opening of insert.hip)
-// datasets/ray_utils.py:45-70 (rays_d = dir_cam @ R^T, rays_o = c2w[:,3]) for
-// the gathered training batch (train.py:85-87), then the single-box AABB
-// test and the near clamp of models/rendering.py:29-31.
+// (shared by the ray-generation kernels of march.hip, the insertion frame
+// opening of insert.hip and the object shade of shade.hip)
+// datasets/ray_utils.py:45-70: rays_d = dir_cam @ R^T of one (3,4) pose P.
+__device__ __forceinline__ void ray_dir(const float* __restrict__ P, const float* __restrict__ dc,
+                                        float* __restrict__ d) {
+    const float d0 = dc[0], d1 = dc[1], d2 = dc[2];
+    // einsum 'n1c,nba->n1a' of rearranged c2w: d_i = sum_c dc_c * R[i][c],
+    // evaluated c-major like the batched matmul (fp32, no contraction).
+#pragma unroll
+    for (int i = 0; i < 3; ++i) d[i] = d0 * P[4 * i + 0] + d1 * P[4 * i + 1] + d2 * P[4 * i + 2];
+}
+
+// ray_dir and rays_o = c2w[:,3] for the gathered training batch
+// (train.py:85-87), then the single-box AABB test and the near clamp of
+// models/rendering.py:29-31.
 __device__ __forceinline__ void gen_ray(const float* __restrict__ P, const float* __restrict__ dc,
                                         const float* __restrict__ center, const float* __restrict__ half_size,
                                         float near, float* __restrict__ ro, float* __restrict__ rd,
                                         float* __restrict__ ht) {
-    const float d0 = dc[0], d1 = dc[1], d2 = dc[2];
-    // einsum 'n1c,nba->n1a' of rearranged c2w: d_i = sum_c dc_c * R[i][c],
-    // evaluated c-major like the batched matmul (fp32, no contraction).
     float d[3], o[3];
+    ray_dir(P, dc, d);
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        d[i] = d0 * P[4 * i + 0] + d1 * P[4 * i + 1] + d2 * P[4 * i + 2];
-        o[i] = P[4 * i + 3];
-    }
+    for (int i = 0; i < 3; ++i) o[i] = P[4 * i + 3];
     const float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
     float t1, t2;
     aabb_t1t2(o, inv, center, half_size, t1, t2);

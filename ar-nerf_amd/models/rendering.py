@@ -236,6 +236,60 @@ def render_insert(model, c2w, directions, H, W, rect, obj_rgb, obj_depth, **kwar
     return rr.render_rect(c2w, rect, obj_rgb, obj_depth)
 
 
+def _insert_renderer(model, directions, H, W, kwargs):
+    """render_insert's cached InsertRenderer for these settings (the same key
+    and construction, so both calls share one renderer per camera), with the
+    model's current parameters and the frame's exposure set."""
+    import renderer as RD
+    esf = kwargs.get('exp_step_factor', 0.)
+    T_threshold, max_samples = kwargs.get('T_threshold', 1e-4), kwargs.get('max_samples', MAX_SAMPLES)
+    radiance = kwargs.get('output_radiance', False)
+    rgb_act = int(model.rgb_mode(radiance))
+    tone_mode = model.tone_mode(radiance)
+    directions = directions.reshape(-1, 3)
+    cache = model.__dict__.setdefault('_insert_renderers', {})
+    key = (int(H), int(W), directions.data_ptr(), float(esf), float(T_threshold), int(max_samples),
+           model.density_bitfield.data_ptr(), rgb_act, tone_mode)
+    rr = cache.get(key)
+    p16 = model._shadow.get()
+    t16 = model._tone_shadow.get() if tone_mode is not None else None
+    if rr is None:
+        if len(cache) >= 4:
+            cache.clear()
+        rr = RD.InsertRenderer(H, W, directions, model.center, model.half_size, model.grid, p16.clone(),
+                               model.density_bitfield, model.cascades, model.scale, model.grid_size,
+                               exp_step_factor=esf, T_threshold=T_threshold, max_samples=max_samples,
+                               iters_per_graph=16, iters_tail=8, rgb_act=rgb_act,
+                               tone16=None if t16 is None else t16.clone(), tone_mode=tone_mode)
+        rr._src = rr._tone_src = None
+        cache[key] = rr
+    _refresh_shadows(rr, p16, t16)
+    if tone_mode is not None:
+        uniform, exposure = _frame_exposure(kwargs)
+        if not uniform:
+            raise ValueError("render_insert_sg takes one exposure per frame")
+        rr.set_exposure(exposure)
+    return rr
+
+
+@torch.no_grad()
+def render_insert_sg(model, c2w, directions, H, W, rect, bbox, normals, obj_depth, lSGs, **kwargs):
+    """render_insert with the object shaded on the device: the app's
+    Insertor.render_object under SG lights (insert/main.py:521-594,
+    shading.sg_shade) into the cached InsertRenderer's own obj_rgb buffer,
+    then the rectangle.  bbox: the model's box (hs, ws, hl, wl), in which the
+    object is shaded; rect: the update range that is rendered (main.py:632);
+    each four ints or a device int32[4] tensor.  normals (H,W,3), obj_depth
+    (H,W), lSGs (L,7).  kwargs: render_insert's, and the materials metal,
+    rough, albedo, decay, clamp01 (default: not output_radiance, the app's
+    `not render_HDR_mapping`)."""
+    shade = {k: kwargs.pop(k) for k in ('metal', 'rough', 'albedo', 'decay') if k in kwargs}
+    shade['clamp01'] = kwargs.pop('clamp01', not kwargs.get('output_radiance', False))
+    rr = _insert_renderer(model, directions, H, W, kwargs)
+    rr.shade_sg(c2w, bbox, normals, obj_depth, lSGs, **shade)
+    return rr.render_rect(c2w, rect)
+
+
 def __render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
     """models/rendering.py:255-298."""
     exp_step_factor = kwargs.get('exp_step_factor', 0.)

@@ -360,6 +360,24 @@ class InsertRenderer(TestRenderer):
         return {"rgb": self.frame_rgb.view(H, W, 3), "depth": self.frame_depth.view(H, W),
                 "pts": self.frame_pts.view(H, W, 3), "total_samples": self.state[RS_TOTAL]}
 
+    @torch.no_grad()
+    def shade_sg(self, c2w, bbox, normals, obj_depth, lSGs, metal=0.9, rough=0.2, albedo=None, decay=None,
+                 clamp01=True):
+        """The frame's object image on the device (shading.sg_shade): obj_depth (H,W) is
+        written to the renderer's buffer and the object, seen from the (3,4) pose c2w inside the model's box
+        bbox = (hs, ws, hl, wl) (four ints or a device int32[4] tensor; not the update rectangle), is shaded
+        under the lights lSGs (L,7) straight into the obj_rgb buffer: no host copy.  A frame is then
+        shade_sg(...) and render_rect(c2w, rect) with obj_rgb = obj_depth = None.  The launch is outside the
+        captured graphs, so L may change from frame to frame.  Returns the obj_rgb buffer as (H,W,3)."""
+        import shading
+        self._pose.copy_(c2w.reshape(3, 4))
+        shading._arg("obj_depth", obj_depth, torch.float32, self.n_rays, f"(H,W) = ({self.H},{self.W})")
+        if obj_depth.data_ptr() != self.obj_depth.data_ptr():
+            self.obj_depth.copy_(obj_depth.reshape(self.obj_depth.shape))
+        return shading.sg_shade(self.H, self.W, self._dirs, self._pose, bbox, normals, self.obj_depth, lSGs,
+                                metal=metal, rough=rough, albedo=albedo, decay=decay, clamp01=clamp01,
+                                out=self.obj_rgb)
+
     def render_frame(self, c2w, obj_rgb=None, obj_depth=None):
         """render_rect over the whole screen (the app's frame after a camera move)."""
         return self.render_rect(c2w, (0, 0, self.H, self.W), obj_rgb, obj_depth)

@@ -331,6 +331,30 @@ int ngp_insert_frame_finish(const int64_t* header, int64_t H, int64_t W, const f
                             const float* rgb, const float* rays_o, const float* rays_d, const float* obj_rgb,
                             float* frame_rgb, float* frame_depth, float* frame_pts, void* stream);
 
+/* ---- object shading for insertion frames -----------------
+ * The SG branch of the insertion app's Insertor.render_object (insert/main.py:
+ * 521-594) with its SG_render_core (insert/render_utils.py:265-375): the
+ * whole-frame obj_rgb (H*W,3) that ngp_insert_frame_finish blends in, shaded
+ * under n_lights spherical-Gaussian lights, one launch, fp32, no temporaries.
+ * bbox: device int32[4] = the model's box (hs, ws, hl, wl), clamped like
+ * ngp_insert_frame_begin's rect.  A pixel is covered when it lies in the box
+ * and obj_depth > 1e-6 (fp32 compare); every other pixel is written 0.
+ * directions (H*W,3) and pose (3,4) give the view direction (normalised, no
+ * epsilon); normals (H*W,3) need not be unit (zero on a covered pixel is out
+ * of contract: 0/0).  lSGs (n_lights,7) = axis, sharpness, rgb amplitude;
+ * decay: null or (H*W,n_lights), multiplies the amplitude per pixel.
+ * Materials: albedo null (ones; albedo_rows 0), one row (albedo_rows 1) or a
+ * map (albedo_rows H*W); metal_map (H*W) or, when null, the scalar metal;
+ * rough_map (H*W), clipped to [0.2, 1], or, when null, the scalar rough as
+ * given.  clamp01: clamp(0,1), else relu.  Lights are summed ascending, in
+ * tiles of NGP_SG_LIGHT_TILE staged in LDS: a pixel's value does not depend
+ * on the launch shape. */
+#define NGP_SG_LIGHT_TILE 64
+int ngp_sg_shade(const int32_t* bbox, int64_t H, int64_t W, const float* directions, const float* pose,
+                 const float* normals, const float* obj_depth, const float* lSGs, int n_lights, const float* decay,
+                 const float* albedo, int albedo_rows, const float* metal_map, float metal, const float* rough_map,
+                 float rough, int clamp01, float* obj_rgb, void* stream);
+
 /* ------------------------------------------------------- light probes */
 /* The insertion app's light probes (insert/main.py:306-407): R rays from each
  * of P scene points, the global light blended in behind them as an SH9
