@@ -1,5 +1,9 @@
-// Occupancy-grid ray-marching step shared by the training / test marchers
-// (march.hip) and the device-resident test render loop (render.hip).
+// The occupancy-grid walk of the training / test marchers (march.hip) and of
+// the device-resident test render loop (render.hip), each part stated once:
+// the probe of one point (probe_cell), the serial walk (march_step,
+// march_walk_serial) and the wave-per-ray lattice walk (lat_build,
+// lat_near_occupied, lat_walk).  The kernels keep what differs between them:
+// the entry test, the sample limit and where an emitted sample is stored.
 // raymarching.cu:11-60,166-234,335-404 of the reference.
 #pragma once
 #pragma clang fp contract(off)
@@ -97,41 +101,24 @@ __device__ __forceinline__ const uint32_t* load_summary(const MarchParams& p, ui
     return lds;
 }
 
-// The occupancy test at t (raymarching.cu:205-221): position, cell, bit.
-// Returns the bit; for an empty cell also the voxel-exit target
-// t_target (:222-228) that the walk then steps past.
-template <bool SIMPLE>
-__device__ __forceinline__ bool march_probe(float t, const float o[3], const float d[3], const float dinv[3],
-                                            const MarchParams& p, float& x, float& y, float& z, float& dt,
-                                            WordCache& wc, float& t_target) {
-    const uint32_t G = (uint32_t)p.grid_size;
-    const uint32_t grid_size3 = G * G * G;
-    const float grid_size_inv = 1.0f / p.grid_size;
-    x = o[0] + t * d[0]; y = o[1] + t * d[1]; z = o[2] + t * d[2];
-    int mip;
-    float mip_bound, mip_bound_inv;
-    if constexpr (SIMPLE) {
-        dt = NGP_SQRT3 / p.max_samples;  // = clamp(t*0, sqrt3/max, 2 sqrt3 scale/G), t finite
-        mip = 0;
-        mip_bound = fminf(0.5f, p.scale);
-        mip_bound_inv = 1 / mip_bound;
-    } else {
-        dt = calc_dt(t, p.esf, p.max_samples, p.grid_size, p.dt_scale);
-        mip = max(mip_from_pos(x, y, z, p.cascades), mip_from_dt(dt, p.grid_size, p.cascades));
-        mip_bound = fminf(scalbnf(1.0f, mip - 1), p.scale);
-        mip_bound_inv = 1 / mip_bound;
-    }
-    const float gm1 = p.grid_size - 1.0f;
-    const int nx = (int)clampf(0.5f * (x * mip_bound_inv + 1) * p.grid_size, 0.0f, gm1);
-    const int ny = (int)clampf(0.5f * (y * mip_bound_inv + 1) * p.grid_size, 0.0f, gm1);
-    const int nz = (int)clampf(0.5f * (z * mip_bound_inv + 1) * p.grid_size, 0.0f, gm1);
-    const uint32_t idx = (uint32_t)mip * grid_size3 + morton3((uint32_t)nx, (uint32_t)ny, (uint32_t)nz);
+// The occupancy test of the point (x, y, z) = o + t d in one cascade, stated
+// once: cell, bitfield word (through the lane's word cache), bit, and for an
+// empty cell the voxel-exit target t_target (raymarching.cu:214-228) that the
+// walk then steps past.  mip_base = mip * G^3 is the cascade's first cell.
+__device__ __forceinline__ bool probe_cell(float t, float x, float y, float z, const float d[3], const float dinv[3],
+                                           const uint8_t* bitfield, uint32_t mip_base, float mip_bound,
+                                           float mip_bound_inv, float grid_f, float grid_size_inv, float gm1,
+                                           WordCache& wc, float& t_target) {
+    const int nx = (int)clampf(0.5f * (x * mip_bound_inv + 1) * grid_f, 0.0f, gm1);
+    const int ny = (int)clampf(0.5f * (y * mip_bound_inv + 1) * grid_f, 0.0f, gm1);
+    const int nz = (int)clampf(0.5f * (z * mip_bound_inv + 1) * grid_f, 0.0f, gm1);
+    const uint32_t idx = mip_base + morton3((uint32_t)nx, (uint32_t)ny, (uint32_t)nz);
     const uint32_t wi = idx >> 6;
     if (wi != wc.idx) {  // bitfield is (C*G^3/8) bytes, G^3 a multiple of 64 for G >= 4
         // an all-empty word is known from the LDS summary: no global load, so
         // a wave crossing empty space never waits on memory
         const bool any = !wc.sum || ((wc.sum[wi >> 5] >> (wi & 31u)) & 1u);
-        wc.word = any ? reinterpret_cast<const uint64_t*>(p.bitfield)[wi] : 0ull;
+        wc.word = any ? reinterpret_cast<const uint64_t*>(bitfield)[wi] : 0ull;
         wc.idx = wi;
     }
     const bool occ = (wc.word >> (idx & 63u)) & 1ull;
@@ -141,6 +128,29 @@ __device__ __forceinline__ bool march_probe(float t, const float o[3], const flo
     const float tz = (((nz + 0.5f + 0.5f * copysignf(1.0f, d[2])) * grid_size_inv * 2 - 1) * mip_bound - z) * dinv[2];
     t_target = t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
     return false;
+}
+
+// The occupancy test at t (raymarching.cu:205-221): position, dt, cascade,
+// then probe_cell.  Returns the bit; for an empty cell also t_target.
+template <bool SIMPLE>
+__device__ __forceinline__ bool march_probe(float t, const float o[3], const float d[3], const float dinv[3],
+                                            const MarchParams& p, float& x, float& y, float& z, float& dt,
+                                            WordCache& wc, float& t_target) {
+    const uint32_t G = (uint32_t)p.grid_size;
+    x = o[0] + t * d[0]; y = o[1] + t * d[1]; z = o[2] + t * d[2];
+    int mip;
+    float mip_bound;
+    if constexpr (SIMPLE) {
+        dt = NGP_SQRT3 / p.max_samples;  // = clamp(t*0, sqrt3/max, 2 sqrt3 scale/G), t finite
+        mip = 0;
+        mip_bound = fminf(0.5f, p.scale);
+    } else {
+        dt = calc_dt(t, p.esf, p.max_samples, p.grid_size, p.dt_scale);
+        mip = max(mip_from_pos(x, y, z, p.cascades), mip_from_dt(dt, p.grid_size, p.cascades));
+        mip_bound = fminf(scalbnf(1.0f, mip - 1), p.scale);
+    }
+    return probe_cell(t, x, y, z, d, dinv, p.bitfield, (uint32_t)mip * (G * G * G), mip_bound, 1 / mip_bound,
+                      (float)p.grid_size, 1.0f / p.grid_size, p.grid_size - 1.0f, wc, t_target);
 }
 
 // march_probe<true>'s per-launch constants, computed once (the wave march
@@ -161,31 +171,13 @@ __device__ __forceinline__ ProbeConsts probe_consts(const MarchParams& p) {
     c.gm1 = uniform_f(p.grid_size - 1.0f);
     return c;
 }
-// march_probe<true> with the constants precomputed: the same expressions,
-// operand for operand (bit-identical)
+// march_probe<true> with the constants precomputed
 __device__ __forceinline__ bool march_probe_simple(float t, const float o[3], const float d[3], const float dinv[3],
                                                    const MarchParams& p, const ProbeConsts& k, WordCache& wc,
                                                    float& t_target) {
-    const uint32_t G = (uint32_t)p.grid_size;
     const float x = o[0] + t * d[0], y = o[1] + t * d[1], z = o[2] + t * d[2];
-    const int nx = (int)clampf(0.5f * (x * k.mip_bound_inv + 1) * k.grid_f, 0.0f, k.gm1);
-    const int ny = (int)clampf(0.5f * (y * k.mip_bound_inv + 1) * k.grid_f, 0.0f, k.gm1);
-    const int nz = (int)clampf(0.5f * (z * k.mip_bound_inv + 1) * k.grid_f, 0.0f, k.gm1);
-    (void)G;
-    const uint32_t idx = morton3((uint32_t)nx, (uint32_t)ny, (uint32_t)nz);
-    const uint32_t wi = idx >> 6;
-    if (wi != wc.idx) {
-        const bool any = !wc.sum || ((wc.sum[wi >> 5] >> (wi & 31u)) & 1u);
-        wc.word = any ? reinterpret_cast<const uint64_t*>(p.bitfield)[wi] : 0ull;
-        wc.idx = wi;
-    }
-    const bool occ = (wc.word >> (idx & 63u)) & 1ull;
-    if (occ) return true;
-    const float tx = (((nx + 0.5f + 0.5f * copysignf(1.0f, d[0])) * k.grid_size_inv * 2 - 1) * k.mip_bound - x) * dinv[0];
-    const float ty = (((ny + 0.5f + 0.5f * copysignf(1.0f, d[1])) * k.grid_size_inv * 2 - 1) * k.mip_bound - y) * dinv[1];
-    const float tz = (((nz + 0.5f + 0.5f * copysignf(1.0f, d[2])) * k.grid_size_inv * 2 - 1) * k.mip_bound - z) * dinv[2];
-    t_target = t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
-    return false;
+    return probe_cell(t, x, y, z, d, dinv, p.bitfield, 0u, k.mip_bound, k.mip_bound_inv, k.grid_f, k.grid_size_inv,
+                      k.gm1, wc, t_target);
 }
 
 template <bool SIMPLE>
@@ -227,6 +219,27 @@ __device__ __forceinline__ bool march_step(float& t, const float o[3], const flo
     return false;
 }
 
+// The serial walk (raymarching.cu:200-234, 366-400), stated once: steps from
+// t while t < t2 and fewer than `limit` samples are out, and calls
+// emit(s, tc, x, y, z, dt, t_after) for sample s at t = tc (t_after: the walk's
+// t behind it).  Returns the number of samples; t is left where the walk
+// stopped.  The training marches' `0 <= t` is the caller's test at entry: t
+// only grows or becomes +inf, so it holds for the whole loop or not at all.
+template <bool SIMPLE, class Emit>
+__device__ __forceinline__ int march_walk_serial(float& t, float t2, int limit, const float o[3], const float d[3],
+                                                 const float dinv[3], const MarchParams& p, WordCache& wc, Emit emit) {
+    int s = 0;
+    float x, y, z, dt;
+    while (t < t2 && s < limit) {
+        const float tc = t;
+        if (march_step<SIMPLE>(t, o, d, dinv, p, x, y, z, dt, wc)) {
+            emit(s, tc, x, y, z, dt, t);
+            s++;
+        }
+    }
+    return s;
+}
+
 __device__ __forceinline__ void load_ray(const float* rays_o, const float* rays_d, int64_t r, float o[3],
                                          float d[3], float dinv[3]) {
 #pragma unroll
@@ -260,11 +273,13 @@ __device__ __forceinline__ float start_t(const float* hits_t, const float* noise
 // points, so lat_build gives 0 a single-point segment and the closed form
 // starts at t_1 = dt.  The walk (march_step) from point k goes to k + 1 when the
 // cell at t_k is occupied, else to the first j > k with t_j >= t_target(k).
-// So one wave takes one ray: lane i evaluates lattice point c + i of a
-// 64-point window (occupancy + jump target, in parallel), then the wave
-// follows the walk's chain through the window with scalar readlanes and
-// writes the visited occupied points with one coalesced store.  Bit-identical
+// So one wave takes one ray (lat_walk): lane i evaluates lattice point c + i
+// of a 64-point window (occupancy + jump target, in parallel), then the wave
+// resolves the walk's chain through the window by pointer doubling and hands
+// the visited occupied points, ranked, to the caller's emit.  Bit-identical
 // to the serial walk; ~8192 waves per batch instead of 128 latency-bound ones.
+// Used by march_slots_wave_kernel (training: (t, dt) into the ray's slots) and
+// by the wave mode of render_march_kernel (sample-major test-render slots).
 //
 // Segment table (per ray, in LDS): segment q starts at lattice index K[q]
 // with value T[q] and advances by I[q] per index until K[q + 1].
@@ -274,8 +289,36 @@ struct LatSeg {
     float T[LSEG], I[LSEG];
 };
 
-__device__ __forceinline__ float lat_t(const LatSeg& sg, int q, int k) {
-    return fmaf((float)(k - sg.K[q]), sg.I[q], sg.T[q]);
+// Conservative early out (exact), wave-wide: points every 0.45 of a 4^3 block
+// along [t0, t2]; the walk's every probe lies within one block of one of
+// them, so if no point's block has an occupied cell within one block (dil:
+// the dilated summary), the walk emits nothing.  Most rays crossing the box
+// miss the object and cost this instead of a full lattice walk.  Returns
+// whether any point is near an occupied block (wave-uniform).
+__device__ __forceinline__ bool lat_near_occupied(const float o[3], const float d[3], float t0, float t2,
+                                                  const MarchParams& p, const uint32_t* dil) {
+    const int lane = threadIdx.x & 63;
+    const float mb = fminf(0.5f, p.scale);
+    const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const float step = 0.45f * (4.0f * 2.0f * mb / p.grid_size) / dn;
+    const int npts = (int)ceilf((t2 - t0) / step) + 1;
+    const float gm1 = p.grid_size - 1.0f, mbi = 1 / mb;
+    bool near = false;
+    for (int j0 = 0; j0 < npts && !near; j0 += 64) {
+        const int j = j0 + lane;
+        bool b = false;
+        if (j < npts) {
+            const float t = fminf(t0 + (float)j * step, t2);
+            const float x = o[0] + t * d[0], y = o[1] + t * d[1], z = o[2] + t * d[2];
+            const int nx = (int)clampf(0.5f * (x * mbi + 1) * p.grid_size, 0.0f, gm1);
+            const int ny = (int)clampf(0.5f * (y * mbi + 1) * p.grid_size, 0.0f, gm1);
+            const int nz = (int)clampf(0.5f * (z * mbi + 1) * p.grid_size, 0.0f, gm1);
+            const uint32_t wi = morton3((uint32_t)nx >> 2, (uint32_t)ny >> 2, (uint32_t)nz >> 2);
+            b = (dil[wi >> 5] >> (wi & 31u)) & 1u;
+        }
+        near = __ballot(b) != 0ull;
+    }
+    return near;
 }
 
 // Builds the segments from t0 (>= 0) until the lattice passes t2 and returns
@@ -328,32 +371,128 @@ __device__ __forceinline__ int lat_build(float t0, float t2, float dt, LatSeg& s
     }
 }
 
-// first j > k with t_j >= T (capped at k_end), k in segment q
-__device__ __forceinline__ int lat_jump(const LatSeg& sg, int nseg, int q, int k, float T, int k_end) {
+// first j > k with t_j >= T, for lane point k with value tk: inside the
+// window's segment [Kq, Kn) (value Tq, increment Iq, its reciprocal invIq, in
+// registers) from one estimate and exact fix-ups; a jump that would leave the
+// segment steps on serially, t_{j+1} = fl(t_j + dt) -- the lattice's own
+// definition (march_step's `do t += dt while (t < t_target)`), exact across
+// any binade boundary.  The first index with t_j >= T is unique, so the
+// estimate only sets the cost.
+__device__ __forceinline__ int lat_jump_seg(int k, float tk, float T, float dt, int k_end, int Kq, int Kn, float Tq,
+                                            float Iq, float invIq) {
     int j = k + 1;
-    while (q + 1 < nseg && j >= sg.K[q + 1]) ++q;
-    while (j < k_end) {
-        const float tj = lat_t(sg, q, j);
-        if (tj >= T) return j;
-        const int send = q + 1 < nseg ? sg.K[q + 1] : k_end;
-        const float need = (T - tj) / sg.I[q];
-        // jump close to the answer, then fix up with exact lattice values
-        int m = need < 4096.f ? max(1, (int)need) : 4096;
-        int jj = min(j + m, send);
-        while (jj > j + 1 && lat_t(sg, q, jj - 1) >= T) --jj;
-        if (jj >= send) {  // target lies beyond this segment
-            if (send >= k_end) return k_end;
-            j = send;
-            ++q;
-            continue;
+    if (j < Kn) {
+        if (fmaf((float)(j - Kq), Iq, Tq) >= T) return j;
+        const float need = (T - fmaf((float)(j - Kq), Iq, Tq)) * invIq;
+        int jj = min(j + (need < 4096.f ? max(1, (int)need) : 4096), Kn);
+        while (jj > j + 1 && fmaf((float)(jj - 1 - Kq), Iq, Tq) >= T) --jj;
+        if (jj < Kn) {
+            while (jj < Kn && fmaf((float)(jj - Kq), Iq, Tq) < T) ++jj;
+            if (jj < Kn) return jj;
         }
-        while (jj < send && lat_t(sg, q, jj) < T) ++jj;
-        if (jj < send) return jj;
-        if (send >= k_end) return k_end;
-        j = send;
-        ++q;
+        // every point of the segment from j on lies below T: continue from its last one
+        j = Kn;
+        tk = fmaf((float)(Kn - 1 - Kq), Iq, Tq);
     }
-    return k_end;
+    float t = tk;
+    j -= 1;  // (t = t_j)
+    do {
+        t = t + dt;
+        ++j;
+    } while (t < T && j < k_end);
+    return min(j, k_end);
+}
+
+// The lattice walk of one ray by one wave (all 64 lanes call it; the ray's
+// o / d / dinv / dt and the table sg / nseg / k_end of lat_build are
+// wave-uniform): windows of 64 lattice points until the walk reaches k_end or
+// `limit` samples are out.  Calls emit(slot, tk, last) on the lane of every
+// emitted point, slot = its index among the ray's samples, tk its t, last =
+// it is the last one this window emits.  Returns the number of samples.  No
+// block barrier inside: waves of a block may take different trip counts.
+template <class Emit>
+__device__ __forceinline__ int lat_walk(const float o[3], const float d[3], const float dinv[3], float dt, int k_end,
+                                        int nseg, const LatSeg& sg, const MarchParams& p, const ProbeConsts& pc,
+                                        WordCache& wc, int limit, Emit emit) {
+    const int lane = threadIdx.x & 63;
+    // the window's segment q0 = [Kq, Kn) in registers (re-read when the window passes Kn)
+    int c = 0, N = 0, q0 = 0;
+    int Kq = 0, Kn = -1;
+    float Tq = 0.f, Iq = 0.f, invIq = 0.f;
+    while (c < k_end && N < limit) {
+        if (c >= Kn) {
+            while (q0 + 1 < nseg && c >= sg.K[q0 + 1]) ++q0;
+            Kq = sg.K[q0];
+            Kn = q0 + 1 < nseg ? sg.K[q0 + 1] : k_end;
+            Tq = uniform_f(sg.T[q0]);
+            Iq = uniform_f(sg.I[q0]);
+            invIq = uniform_f(1.0f / Iq);
+        }
+        const int k = c + lane;
+        const bool live = k < k_end;
+        bool occ = false;
+        int nxt = k_end;
+        float tk = 0.f;
+        if (live) {
+            if (k < Kn) {
+                tk = fmaf((float)(k - Kq), Iq, Tq);
+            } else {  // past the window's segment (the window straddles a binade): step on from its last point
+                float t = fmaf((float)(Kn - 1 - Kq), Iq, Tq);
+                for (int i = Kn; i <= k; ++i) t = t + dt;
+                tk = t;
+            }
+            float T;
+            occ = march_probe_simple(tk, o, d, dinv, p, pc, wc, T);
+            nxt = occ ? k + 1 : lat_jump_seg(k, tk, T, dt, k_end, Kq, Kn, Tq, Iq, invIq);
+        }
+        const uint64_t occm = __ballot(occ);
+        const uint64_t livem = __ballot(live);
+        // The walk's chain through the window.  A window whose live points are all
+        // occupied is visited whole (successor k + 1 throughout).  Otherwise, in
+        // parallel: J_b(i) = the 2^b-th successor of window point i (64 = out of the
+        // window), built by pointer doubling; every lane then climbs from point 0 with
+        // binary lifting to the last chain point <= itself -- it is on the chain iff
+        // that is itself (successors only move forward).  (A scalar hop per empty
+        // chain point instead: ~14 hops per window in empty space, 30 SALU
+        // instructions and 3 branches each, the kernel 1.6x slower with every wave
+        // resident -- the CU's scalar unit is shared, profiles/r06/march_variants.txt.)
+        uint64_t vis;
+        int pnt;
+        if (occm == livem) {
+            vis = livem;
+            pnt = (livem >> 63) ? c + 64 : k_end;
+        } else {
+            int J[6];
+            J[0] = live ? min(nxt - c, 64) : 64;
+#pragma unroll
+            for (int b = 1; b < 6; ++b) {
+                const int prev = J[b - 1];
+                const int v = __builtin_amdgcn_ds_bpermute(min(prev, 63) << 2, prev);
+                J[b] = prev >= 64 ? 64 : v;
+            }
+            int cu = 0;
+#pragma unroll
+            for (int b = 5; b >= 0; --b) {
+                const int v = __builtin_amdgcn_ds_bpermute(min(cu, 63) << 2, J[b]);
+                const int to = cu >= 64 ? 64 : v;
+                if (to <= lane) cu = to;
+            }
+            vis = __ballot(cu == lane);
+            const int last = 63 - __builtin_clzll(vis);  // the chain's last point in the window
+            pnt = __builtin_amdgcn_readlane(nxt, last);  // k_end if it ends the walk
+        }
+        vis &= occm;
+        // emit the chain's occupied points, at most up to the limit
+        const int room = limit - N;
+        const int ne = min(__builtin_popcountll(vis), room);
+        if ((vis >> lane) & 1ull) {
+            const int rank = __builtin_popcountll(vis & ((1ull << lane) - 1ull));
+            if (rank < room) emit(N + rank, tk, rank == ne - 1);
+        }
+        N += ne;
+        c = pnt;
+    }
+    return N;
 }
 
 }  // namespace ngp

@@ -216,11 +216,10 @@ __global__ void __launch_bounds__(64) march_count_kernel(const float* __restrict
     load_ray(rays_o, rays_d, r, o, d, dinv);
     const float t2 = hits_t[2 * r + 1];
     float t = start_t(hits_t, noise, r, p);
-    int N = 0;
-    float x, y, z, dt;
     WordCache wc;
-    while (0 <= t && t < t2 && N < p.max_samples) N += march_step<SIMPLE>(t, o, d, dinv, p, x, y, z, dt, wc) ? 1 : 0;
-    counts[r] = N;
+    counts[r] = 0 <= t ? march_walk_serial<SIMPLE>(t, t2, p.max_samples, o, d, dinv, p, wc,
+                                                   [](int, float, float, float, float, float, float) {})
+                       : 0;
 }
 
 // Exclusive scan of the per-ray counts -> ray-ordered rays_a + total, in one
@@ -298,20 +297,15 @@ __global__ void __launch_bounds__(64) march_write_kernel(const float* __restrict
     load_ray(rays_o, rays_d, r, o, d, dinv);
     const float t2 = hits_t[2 * r + 1];
     float t = start_t(hits_t, noise, r, p);
-    int samples = 0;
-    float x, y, z, dt;
     WordCache wc;
-    while (t < t2 && samples < N) {
-        const float tc = t;
-        if (march_step<SIMPLE>(t, o, d, dinv, p, x, y, z, dt, wc)) {
-            const int64_t s = start + samples;
-            xyzs[3 * s] = x; xyzs[3 * s + 1] = y; xyzs[3 * s + 2] = z;
-            dirs[3 * s] = d[0]; dirs[3 * s + 1] = d[1]; dirs[3 * s + 2] = d[2];
-            ts[s] = tc;
-            deltas[s] = dt;
-            samples++;
-        }
-    }
+    march_walk_serial<SIMPLE>(t, t2, N, o, d, dinv, p, wc,
+                              [&](int k, float tc, float x, float y, float z, float dt, float) {
+                                  const int64_t s = start + k;
+                                  xyzs[3 * s] = x; xyzs[3 * s + 1] = y; xyzs[3 * s + 2] = z;
+                                  dirs[3 * s] = d[0]; dirs[3 * s + 1] = d[1]; dirs[3 * s + 2] = d[2];
+                                  ts[s] = tc;
+                                  deltas[s] = dt;
+                              });
 }
 
 // Single-pass training march: the walk of raymarching.cu:200-234 run once,
@@ -342,72 +336,17 @@ __global__ void __launch_bounds__(256) march_slots_kernel(const float* __restric
     load_ray(rays_o, rays_d, r, o, d, dinv);
     const float t2 = hits_t[2 * r + 1];
     float t = start_t(hits_t, noise, r, p);
-    int N = 0;
-    float x, y, z, dt;
     float* st = slot_t + r * (int64_t)p.max_samples;
     float* sd = slot_dt + r * (int64_t)p.max_samples;
-    while (0 <= t && t < t2 && N < p.max_samples) {
-        const float tc = t;
-        if (march_step<SIMPLE>(t, o, d, dinv, p, x, y, z, dt, wc)) {
-            st[N] = tc;
-            sd[N] = dt;
-            N++;
-        }
-    }
-    counts[r] = N;
+    counts[r] = 0 <= t ? march_walk_serial<SIMPLE>(t, t2, p.max_samples, o, d, dinv, p, wc,
+                                                   [&](int k, float tc, float, float, float, float dt, float) {
+                                                       st[k] = tc;
+                                                       sd[k] = dt;
+                                                   })
+                       : 0;
 }
 
-// (lattice helpers LatSeg / lat_build / lat_jump: march.h)
-
-// The serial walk of one ray on lane 0 (a lattice whose segment table
-// overflows: dt below half an ulp of t, or more than LSEG binades -- never on
-// the object scenes; kept out of line so its registers do not count against
-// the lattice loop's).
-
-
-// first j > k with t_j >= T, for lane point k with value tk: inside the
-// window's segment [Kq, Kn) (value Tq, increment Iq, its reciprocal invIq, in
-// registers) from one estimate and exact fix-ups; a jump that would leave the
-// segment steps on serially, t_{j+1} = fl(t_j + dt) -- the lattice's own
-// definition (march_step's `do t += dt while (t < t_target)`), exact across
-// any binade boundary.  The first index with t_j >= T is unique, so the
-// estimate only sets the cost.
-__device__ __forceinline__ int lat_jump_seg(int k, float tk, float T, float dt, int k_end, int Kq, int Kn, float Tq,
-                                            float Iq, float invIq) {
-    int j = k + 1;
-    if (j < Kn) {
-        if (fmaf((float)(j - Kq), Iq, Tq) >= T) return j;
-        const float need = (T - fmaf((float)(j - Kq), Iq, Tq)) * invIq;
-        int jj = min(j + (need < 4096.f ? max(1, (int)need) : 4096), Kn);
-        while (jj > j + 1 && fmaf((float)(jj - 1 - Kq), Iq, Tq) >= T) --jj;
-        if (jj < Kn) {
-            while (jj < Kn && fmaf((float)(jj - Kq), Iq, Tq) < T) ++jj;
-            if (jj < Kn) return jj;
-        }
-        // every point of the segment from j on lies below T: continue from its last one
-        j = Kn;
-        tk = fmaf((float)(Kn - 1 - Kq), Iq, Tq);
-    }
-    float t = tk;
-    j -= 1;  // (t = t_j)
-    do {
-        t = t + dt;
-        ++j;
-    } while (t < T && j < k_end);
-    return min(j, k_end);
-}
-
-// (lane 0: the ray's samples into its slot_t / slot_dt range)
-__device__ __forceinline__ int march_serial_lane(const float o[3], const float d[3], const float dinv[3], float t,
-                                              float t2, const MarchParams& p, WordCache& wc, float* st, float* sd) {
-    float x, y, z, dts;
-    int N = 0;
-    while (0 <= t && t < t2 && N < p.max_samples) {
-        const float tc = t;
-        if (march_step<true>(t, o, d, dinv, p, x, y, z, dts, wc)) { st[N] = tc; sd[N] = dts; N++; }
-    }
-    return N;
-}
+// (lattice helpers LatSeg / lat_build / lat_near_occupied / lat_walk: march.h)
 
 // 8 waves per SIMD (64 VGPRs): every wave of an 8192-ray batch resident at once, no second
 // dispatch round (73 -> 57 us alone; 7 waves at 65 VGPRs measured 58 us and -0.8 % end to end,
@@ -444,36 +383,9 @@ __global__ void __launch_bounds__(256, 8) march_slots_wave_kernel(const float* _
             if (lane == 0) counts[r] = 0;
             continue;
         }
-        // Conservative early out (exact): points every half 4^3-block along
-        // [t0, t2]; the walk's every probe lies within one block of one of them,
-        // so if no point's block has an occupied cell within one block
-        // (dilated summary), the walk emits nothing.  Most rays crossing the box
-        // miss the object and cost this instead of a full lattice walk.
-        if (wc.dil) {
-            const float mb = fminf(0.5f, p.scale);
-            const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-            const float step = 0.45f * (4.0f * 2.0f * mb / p.grid_size) / dn;
-            const int npts = (int)ceilf((t2 - t0) / step) + 1;
-            const float gm1 = p.grid_size - 1.0f, mbi = 1 / mb;
-            bool near = false;
-            for (int j0 = 0; j0 < npts && !near; j0 += 64) {
-                const int j = j0 + lane;
-                bool b = false;
-                if (j < npts) {
-                    const float t = fminf(t0 + (float)j * step, t2);
-                    const float x = o[0] + t * d[0], y = o[1] + t * d[1], z = o[2] + t * d[2];
-                    const int nx = (int)clampf(0.5f * (x * mbi + 1) * p.grid_size, 0.0f, gm1);
-                    const int ny = (int)clampf(0.5f * (y * mbi + 1) * p.grid_size, 0.0f, gm1);
-                    const int nz = (int)clampf(0.5f * (z * mbi + 1) * p.grid_size, 0.0f, gm1);
-                    const uint32_t wi = morton3((uint32_t)nx >> 2, (uint32_t)ny >> 2, (uint32_t)nz >> 2);
-                    b = (wc.dil[wi >> 5] >> (wi & 31u)) & 1u;
-                }
-                near = __ballot(b) != 0ull;
-            }
-            if (!near) {
-                if (lane == 0) counts[r] = 0;
-                    continue;
-            }
+        if (wc.dil && !lat_near_occupied(o, d, t0, t2, p, wc.dil)) {  // exact early out
+            if (lane == 0) counts[r] = 0;
+            continue;
         }
         LatSeg& sg = segs[w];
         int nseg = 0;
@@ -481,90 +393,22 @@ __global__ void __launch_bounds__(256, 8) march_slots_wave_kernel(const float* _
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (k_end < 0) {  // segment table overflow: the serial walk on lane 0
-            if (lane == 0) counts[r] = march_serial_lane(o, d, dinv, t0, t2, p, wc, st, sd);
+        const auto emit = [&](int slot, float tk, bool) {
+            st[slot] = tk;
+            sd[slot] = dt;
+        };
+        // segment table overflow (dt below half an ulp of t, or more than LSEG binades -- never on the object
+        // scenes): the serial walk on lane 0
+        if (k_end < 0) {
+            if (lane == 0) {
+                float t = t0;
+                counts[r] = march_walk_serial<true>(
+                    t, t2, p.max_samples, o, d, dinv, p, wc,
+                    [&](int k, float tc, float, float, float, float, float) { emit(k, tc, false); });
+            }
             continue;
         }
-        // the window's segment q0 = [Kq, Kn) in registers (re-read when the window passes Kn)
-        int c = 0, N = 0, q0 = 0;
-        int Kq = 0, Kn = -1;
-        float Tq = 0.f, Iq = 0.f, invIq = 0.f;
-        while (c < k_end && N < p.max_samples) {
-            if (c >= Kn) {
-                while (q0 + 1 < nseg && c >= sg.K[q0 + 1]) ++q0;
-                Kq = sg.K[q0];
-                Kn = q0 + 1 < nseg ? sg.K[q0 + 1] : k_end;
-                Tq = uniform_f(sg.T[q0]);
-                Iq = uniform_f(sg.I[q0]);
-                invIq = uniform_f(1.0f / Iq);
-            }
-            const int k = c + lane;
-            const bool live = k < k_end;
-            bool occ = false;
-            int nxt = k_end;
-            float tk = 0.f;
-            if (live) {
-                if (k < Kn) {
-                    tk = fmaf((float)(k - Kq), Iq, Tq);
-                } else {  // past the window's segment (the window straddles a binade): step on from its last point
-                    float t = fmaf((float)(Kn - 1 - Kq), Iq, Tq);
-                    for (int i = Kn; i <= k; ++i) t = t + dt;
-                    tk = t;
-                }
-                float T;
-                occ = march_probe_simple(tk, o, d, dinv, p, pc, wc, T);
-                nxt = occ ? k + 1 : lat_jump_seg(k, tk, T, dt, k_end, Kq, Kn, Tq, Iq, invIq);
-            }
-            const uint64_t occm = __ballot(occ);
-            const uint64_t livem = __ballot(live);
-            // The walk's chain through the window.  A window whose live points are all
-            // occupied is visited whole (successor k + 1 throughout).  Otherwise, in
-            // parallel: J_b(i) = the 2^b-th successor of window point i (64 = out of the
-            // window), built by pointer doubling; every lane then climbs from point 0 with
-            // binary lifting to the last chain point <= itself -- it is on the chain iff
-            // that is itself (successors only move forward).  (A scalar hop per empty
-            // chain point instead: ~14 hops per window in empty space, 30 SALU
-            // instructions and 3 branches each, the kernel 1.6x slower with every wave
-            // resident -- the CU's scalar unit is shared, profiles/r06/march_variants.txt.)
-            uint64_t vis;
-            int pnt;
-            if (occm == livem) {
-                vis = livem;
-                pnt = (livem >> 63) ? c + 64 : k_end;
-            } else {
-                int J[6];
-                J[0] = live ? min(nxt - c, 64) : 64;
-#pragma unroll
-                for (int b = 1; b < 6; ++b) {
-                    const int prev = J[b - 1];
-                    const int v = __builtin_amdgcn_ds_bpermute(min(prev, 63) << 2, prev);
-                    J[b] = prev >= 64 ? 64 : v;
-                }
-                int cu = 0;
-#pragma unroll
-                for (int b = 5; b >= 0; --b) {
-                    const int v = __builtin_amdgcn_ds_bpermute(min(cu, 63) << 2, J[b]);
-                    const int to = cu >= 64 ? 64 : v;
-                    if (to <= lane) cu = to;
-                }
-                vis = __ballot(cu == lane);
-                const int last = 63 - __builtin_clzll(vis);  // the chain's last point in the window
-                pnt = __builtin_amdgcn_readlane(nxt, last);  // k_end if it ends the walk
-            }
-            vis &= occm;
-            // emit the chain's occupied points, at most up to max_samples
-            const int room = p.max_samples - N;
-            const int nv = __builtin_popcountll(vis);
-            if ((vis >> lane) & 1ull) {
-                const int rank = __builtin_popcountll(vis & ((1ull << lane) - 1ull));
-                if (rank < room) {
-                    st[N + rank] = tk;
-                    sd[N + rank] = dt;
-                }
-            }
-            N += min(nv, room);
-            c = pnt;
-        }
+        const int N = lat_walk(o, d, dinv, dt, k_end, nseg, sg, p, pc, wc, p.max_samples, emit);
         if (lane == 0) counts[r] = N;
     }
     NGP_PROBE_END();
@@ -621,21 +465,16 @@ __global__ void __launch_bounds__(64) march_test_kernel(const float* __restrict_
     load_ray(rays_o, rays_d, r, o, d, dinv);
     float t = hits_t[2 * r];
     const float t2 = hits_t[2 * r + 1];
-    int s = 0;
-    float x, y, z, dt;
     const int64_t base = n * (int64_t)N_samples;
-    while (t < t2 && s < N_samples) {
-        const float tc = t;
-        if (march_step<SIMPLE>(t, o, d, dinv, p, x, y, z, dt, wc)) {
-            const int64_t q = base + s;
-            xyzs[3 * q] = x; xyzs[3 * q + 1] = y; xyzs[3 * q + 2] = z;
-            dirs[3 * q] = d[0]; dirs[3 * q + 1] = d[1]; dirs[3 * q + 2] = d[2];
-            ts[q] = tc;
-            deltas[q] = dt;
-            hits_t[2 * r] = t;  // raymarching.cu:390
-            s++;
-        }
-    }
+    const int s = march_walk_serial<SIMPLE>(t, t2, N_samples, o, d, dinv, p, wc,
+                                            [&](int k, float tc, float x, float y, float z, float dt, float t_after) {
+                                                const int64_t q = base + k;
+                                                xyzs[3 * q] = x; xyzs[3 * q + 1] = y; xyzs[3 * q + 2] = z;
+                                                dirs[3 * q] = d[0]; dirs[3 * q + 1] = d[1]; dirs[3 * q + 2] = d[2];
+                                                ts[q] = tc;
+                                                deltas[q] = dt;
+                                                hits_t[2 * r] = t_after;  // raymarching.cu:390
+                                            });
     for (int k = s; k < N_samples; ++k) {
         const int64_t q = base + k;
         xyzs[3 * q] = 0.f; xyzs[3 * q + 1] = 0.f; xyzs[3 * q + 2] = 0.f;

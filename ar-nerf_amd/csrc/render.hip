@@ -7,11 +7,12 @@
 //   render_iter_kernel      N_alive = state[p]; stop if 0 or samples >= budget;
 //                           N_samples = max(min(N_rays // N_alive, 64), min_samples)
 //                           (rendering.py:188-195)
-//   render_march_kernel     raymarching_test for the alive rays (raymarching.cu:335-404,
-//                           identical walk to march_test_kernel) into SAMPLE-MAJOR
-//                           slots [s*N_alive + n] (lane-per-ray stores and the
+//   render_march_kernel     raymarching_test for the alive rays (raymarching.cu:335-404) into
+//                           SAMPLE-MAJOR slots [s*N_alive + n] (lane-per-ray stores and the
 //                           composite's loads coalesce across lanes); appends the valid slots to a sample
-//                           list (the reference's valid_mask, rendering.py:204)
+//                           list (the reference's valid_mask, rendering.py:204).  Both walks are
+//                           march.h's: march_walk_serial, one lane per ray (as march_test_kernel),
+//                           or lat_walk, one wave per ray (as march_slots_wave_kernel)
 //   (field kernels)         ngp_hash_encode + ngp_field_mlp_forward over the list
 //   render_composite_kernel composite_test_fw (volumerendering.cu:204-284) and the
 //                           alive compaction (rendering.py:236) into list p^1
@@ -135,12 +136,13 @@ __device__ __forceinline__ void block_append_k(const int (&cnt)[CRPT], int64_t (
 // ---- wave-per-ray mode (SIMPLE launches, N_samples >= WAVE_NS) ----------
 // Late iterations have few alive rays with many samples each: one lane per
 // ray leaves most of the chip idle while each lane walks ~N_samples occupied
-// points serially.  Here one wave takes one ray and walks it with the
-// lattice machinery of march_slots_wave_kernel (march.hip: the fp32 t-lattice
-// in closed form per binade, a 64-point window evaluated in parallel, the
-// walk's chain resolved by pointer doubling) -- the same points as the serial
-// walk, bit for bit.  Sample indices are staged in LDS and appended with one
-// global atomic per block flush.
+// points serially.  Here one wave takes one ray and walks it with the same
+// lat_near_occupied / lat_build / lat_walk (march.h) as the training march's
+// march_slots_wave_kernel -- the same points as the serial walk, bit for bit.
+// What is the render's own: the entry test (t0 < t2; a negative t0 takes the
+// serial walk on lane 0, like a table overflow), N_samples as the limit, the
+// sample-major emit with hits_t left behind the last sample, and the sample
+// indices staged in LDS and appended with one global atomic per block flush.
 constexpr int WAVE_NS = 16;  // N_samples threshold of the wave-per-ray mode (profiles/r01/render/wave_ns_ab.txt)
 constexpr int STAGE = 2048;
 
@@ -169,8 +171,10 @@ __device__ void render_march_waves(const float* __restrict__ rays_o, const float
                                    const int32_t* __restrict__ alive, float* __restrict__ xyzs,
                                    float* __restrict__ dirs, float* __restrict__ deltas, float* __restrict__ ts,
                                    int32_t* __restrict__ n_eff, int32_t* __restrict__ sample_idx, WaveLds& L) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (wave-uniform: the ray's setup is scalar)
     const float dt = NGP_SQRT3 / p.max_samples;
+    const ProbeConsts pc = probe_consts(p);
     if (threadIdx.x == 0) L.nst = 0;
     __syncthreads();
     for (int64_t b0 = (int64_t)blockIdx.x * 4; b0 < n_alive; b0 += (int64_t)gridDim.x * 4) {  // block-uniform
@@ -179,113 +183,37 @@ __device__ void render_march_waves(const float* __restrict__ rays_o, const float
             const int64_t r = alive[n];
             float o[3], d[3], dinv[3];
             load_ray(rays_o, rays_d, r, o, d, dinv);
-            const float t0 = hits_t[2 * r], t2 = hits_t[2 * r + 1];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { o[i] = uniform_f(o[i]); d[i] = uniform_f(d[i]); dinv[i] = uniform_f(dinv[i]); }
+            const float t0 = uniform_f(hits_t[2 * r]), t2 = uniform_f(hits_t[2 * r + 1]);
             int N = 0;
-            bool near = t0 < t2;  // raymarching.cu:366 loop condition at entry
-            if (near && wc.dil) {
-                // exact early out (march_slots_wave_kernel): no occupied block
-                // within one block of the segment -> the walk emits nothing
-                const float mb = fminf(0.5f, p.scale);
-                const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-                const float step = 0.45f * (4.0f * 2.0f * mb / p.grid_size) / dn;
-                const int npts = (int)ceilf((t2 - t0) / step) + 1;
-                const float gm1 = p.grid_size - 1.0f, mbi = 1 / mb;
-                bool any = false;
-                for (int j0 = 0; j0 < npts && !any; j0 += 64) {
-                    const int j = j0 + lane;
-                    bool b = false;
-                    if (j < npts) {
-                        const float t = fminf(t0 + (float)j * step, t2);
-                        const float x = o[0] + t * d[0], y = o[1] + t * d[1], z = o[2] + t * d[2];
-                        const int nx = (int)clampf(0.5f * (x * mbi + 1) * p.grid_size, 0.0f, gm1);
-                        const int ny = (int)clampf(0.5f * (y * mbi + 1) * p.grid_size, 0.0f, gm1);
-                        const int nz = (int)clampf(0.5f * (z * mbi + 1) * p.grid_size, 0.0f, gm1);
-                        const uint32_t wi = morton3((uint32_t)nx >> 2, (uint32_t)ny >> 2, (uint32_t)nz >> 2);
-                        b = (wc.dil[wi >> 5] >> (wi & 31u)) & 1u;
-                    }
-                    any = __ballot(b) != 0ull;
-                }
-                near = any;
-            }
-            if (near) {
+            // raymarching.cu:366 loop condition at entry, then the exact early out
+            if (t0 < t2 && (!wc.dil || lat_near_occupied(o, d, t0, t2, p, wc.dil))) {
                 LatSeg& sg = L.segs[w];
                 int nseg = 0;
                 const int k_end = t0 >= 0 ? lat_build(t0, t2, dt, sg, nseg, lane == 0) : -1;
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                if (k_end < 0) {  // table overflow: the serial walk on lane 0
+                // sample-major slots; x = o + tk d is the probe's own expression (no contraction)
+                const auto emit = [&](int slot, float tk, bool last) {
+                    const int64_t q = slot * n_alive + n;
+                    xyzs[3 * q] = o[0] + tk * d[0]; xyzs[3 * q + 1] = o[1] + tk * d[1]; xyzs[3 * q + 2] = o[2] + tk * d[2];
+                    dirs[3 * q] = d[0]; dirs[3 * q + 1] = d[1]; dirs[3 * q + 2] = d[2];
+                    ts[q] = tk;
+                    deltas[q] = dt;
+                    if (last) hits_t[2 * r] = tk + dt;  // raymarching.cu:390: t after the last emitted sample
+                };
+                if (k_end < 0) {  // negative t0 or table overflow: the serial walk on lane 0
                     if (lane == 0) {
-                        float t = t0, x, y, z, dts, t_emit = t0;
-                        while (t < t2 && N < Ns) {
-                            const float tc = t;
-                            if (march_step<true>(t, o, d, dinv, p, x, y, z, dts, wc)) {
-                                t_emit = t;
-                                const int64_t q = N * n_alive + n;
-                                xyzs[3 * q] = x; xyzs[3 * q + 1] = y; xyzs[3 * q + 2] = z;
-                                dirs[3 * q] = d[0]; dirs[3 * q + 1] = d[1]; dirs[3 * q + 2] = d[2];
-                                ts[q] = tc;
-                                deltas[q] = dts;
-                                N++;
-                            }
-                        }
-                        if (N) hits_t[2 * r] = t_emit;
+                        float t = t0;
+                        N = march_walk_serial<true>(
+                            t, t2, Ns, o, d, dinv, p, wc,
+                            [&](int k, float tc, float, float, float, float, float) { emit(k, tc, true); });
                     }
                     N = __builtin_amdgcn_readfirstlane(N);
                 } else {
-                    int c = 0, q0 = 0;
-                    while (c < k_end && N < Ns) {
-                        while (q0 + 1 < nseg && c >= sg.K[q0 + 1]) ++q0;
-                        const int k = c + lane;
-                        int q = q0;
-                        while (q + 1 < nseg && k >= sg.K[q + 1]) ++q;
-                        const bool live = k < k_end;
-                        const float tk = live ? lat_t(sg, q, k) : 0.f;
-                        bool occ = false;
-                        int nxt = k_end;
-                        float x = 0.f, y = 0.f, z = 0.f;
-                        if (live) {
-                            float dts, T;
-                            occ = march_probe<true>(tk, o, d, dinv, p, x, y, z, dts, wc, T);
-                            nxt = occ ? k + 1 : lat_jump(sg, nseg, q, k, T, k_end);
-                        }
-                        const uint64_t occm = __ballot(occ && live);
-                        int J[6];
-                        J[0] = live ? min(nxt - c, 64) : 64;
-#pragma unroll
-                        for (int b = 1; b < 6; ++b) {
-                            const int prev = J[b - 1];
-                            const int v = __builtin_amdgcn_ds_bpermute(min(prev, 63) << 2, prev);
-                            J[b] = prev >= 64 ? 64 : v;
-                        }
-                        int cur = 0;
-#pragma unroll
-                        for (int b = 5; b >= 0; --b) {
-                            const int v = __builtin_amdgcn_ds_bpermute(min(cur, 63) << 2, J[b]);
-                            const int to = cur >= 64 ? 64 : v;
-                            if (to <= lane) cur = to;
-                        }
-                        uint64_t vis = __ballot(cur == lane);
-                        const int last = 63 - __builtin_clzll(vis);
-                        const int pnt = __builtin_amdgcn_readlane(nxt, last);
-                        vis &= occm;
-                        const int room = Ns - N;
-                        const int nv = __builtin_popcountll(vis);
-                        const int ne = min(nv, room);
-                        if ((vis >> lane) & 1ull) {
-                            const int rank = __builtin_popcountll(vis & ((1ull << lane) - 1ull));
-                            if (rank < room) {
-                                const int64_t qq = (N + rank) * n_alive + n;
-                                xyzs[3 * qq] = x; xyzs[3 * qq + 1] = y; xyzs[3 * qq + 2] = z;
-                                dirs[3 * qq] = d[0]; dirs[3 * qq + 1] = d[1]; dirs[3 * qq + 2] = d[2];
-                                ts[qq] = tk;
-                                deltas[qq] = dt;
-                                if (rank == ne - 1) hits_t[2 * r] = tk + dt;  // raymarching.cu:390
-                            }
-                        }
-                        N += ne;
-                        c = pnt;
-                    }
+                    N = lat_walk(o, d, dinv, dt, k_end, nseg, sg, p, pc, wc, Ns, emit);
                 }
             }
             int base = 0;
@@ -342,19 +270,16 @@ __global__ void __launch_bounds__(256) render_march_kernel(const float* __restri
             load_ray(rays_o, rays_d, r, o, d, dinv);
             float t = hits_t[2 * r];
             const float t2 = hits_t[2 * r + 1];
-            float x, y, z, dt, t_emit = t;
-            while (t < t2 && s < Ns) {  // raymarching.cu:366-400
-                const float tc = t;
-                if (march_step<SIMPLE>(t, o, d, dinv, p, x, y, z, dt, wc)) {
-                    t_emit = t;
-                    const int64_t q = s * n_alive + n;  // sample-major: lanes' stores coalesce
-                    xyzs[3 * q] = x; xyzs[3 * q + 1] = y; xyzs[3 * q + 2] = z;
-                    dirs[3 * q] = d[0]; dirs[3 * q + 1] = d[1]; dirs[3 * q + 2] = d[2];
-                    ts[q] = tc;
-                    deltas[q] = dt;
-                    s++;
-                }
-            }
+            float t_emit = t;
+            s = march_walk_serial<SIMPLE>(t, t2, Ns, o, d, dinv, p, wc,  // raymarching.cu:366-400
+                                          [&](int k, float tc, float x, float y, float z, float dt, float t_after) {
+                                              t_emit = t_after;
+                                              const int64_t q = k * n_alive + n;  // sample-major: lanes' stores coalesce
+                                              xyzs[3 * q] = x; xyzs[3 * q + 1] = y; xyzs[3 * q + 2] = z;
+                                              dirs[3 * q] = d[0]; dirs[3 * q + 1] = d[1]; dirs[3 * q + 2] = d[2];
+                                              ts[q] = tc;
+                                              deltas[q] = dt;
+                                          });
             if (s) hits_t[2 * r] = t_emit;  // raymarching.cu:390: t after the last emitted sample
             n_eff[n] = s;
         }

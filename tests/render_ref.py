@@ -20,6 +20,7 @@ import functools
 import math
 import types
 
+import numpy as np
 import torch
 
 import composite_ref as CR
@@ -28,17 +29,17 @@ from capi import C
 
 # ------------------------------------------------- mirrored kernel constants
 STATE_WORDS = C["NGP_RENDER_STATE_WORDS"]
-RS_ALIVE0, RS_ALIVE1, RS_SAMPLES, RS_NS, RS_ACTIVE, RS_VALID, RS_TOTAL, RS_ITERS = range(8)  # render.hip:28-29
-NS_MAX = 64                # render.hip:58   N_samples = min(N_rays // N_alive, 64)
-BLOCK = 256                # render.hip:308  __launch_bounds__(256) of every loop kernel
-WAVE_RAYS = 4              # render.hip:178  rays per block per trip of the wave-per-ray mode (one per wave)
-CRPT = 4                   # render.hip:101  rays per thread per composite pass
+RS_ALIVE0, RS_ALIVE1, RS_SAMPLES, RS_NS, RS_ACTIVE, RS_VALID, RS_TOTAL, RS_ITERS = range(8)  # march.h:535-536
+NS_MAX = 64                # render.hip:57   N_samples = min(N_rays // N_alive, 64)
+BLOCK = 256                # render.hip:234  __launch_bounds__(256) of every loop kernel
+WAVE_RAYS = 4              # render.hip:180  rays per block per trip of the wave-per-ray mode (one per wave)
+CRPT = 4                   # render.hip:100  rays per thread per composite pass
 WAVE_NS = 16               # render.hip:146  N_samples from which a SIMPLE march runs wave-per-ray
 STAGE = 2048               # render.hip:147  staged sample indices per block
-FLUSH_SLACK = 4 * 64       # render.hip:302  flush when nst > STAGE - 4 * 64
-MARCH_BLOCKS = 2048        # render.hip:487  grid cap of the march
-COMPOSITE_BLOCKS = 1024    # render.hip:506  grid cap of the composite
-LSEG = 32                  # march.h:235    lattice segments per ray
+FLUSH_SLACK = 4 * 64       # render.hip:228  flush when nst > STAGE - 4 * 64
+MARCH_BLOCKS = 2048        # render.hip:383  grid cap of the march
+COMPOSITE_BLOCKS = 1024    # render.hip:440  grid cap of the composite
+LSEG = 32                  # march.h:286    lattice segments per ray
 NEAR = 0.01                # models/rendering.py NEAR_DISTANCE
 
 
@@ -416,6 +417,23 @@ def march_set_ref(name, iteration=0):
     ht = s.ht if iteration == 0 else march_set_ref(name, iteration - 1).hits_t
     return march_ref(s.o, s.d, ht, s.alive, bitfield(s.bf_kind, c["cascades"], c["grid"]), c["cascades"], c["scale"],
                      c["esf"], c["grid"], c["max_samples"], s.Ns, s.skip)
+
+
+def segment_crossings(rays_ts, dt):
+    """What a set gives the lattice walk's register-held segment (a segment is the lattice inside one binade
+    [2^e, 2^(e+1)); e = floor(log2 t) over t > 0).  rays_ts: per ray, its emitted ts in walk order.  Returns the
+    numbers of rays (a) whose emitted ts span a power of two -- a window that straddles a segment -- and (b) with two
+    consecutive emitted ts more than 1.5 dt apart in different binades -- a jump that leaves its segment."""
+    a = b = 0
+    for ts in rays_ts:
+        ts = np.asarray(ts, dtype=np.float32)
+        ts = ts[ts > 0]
+        if len(ts) < 2:
+            continue
+        e = np.frexp(ts)[1]
+        a += int(e.min() != e.max())
+        b += int(((np.diff(ts.astype(np.float64)) > 1.5 * dt) & (np.diff(e) != 0)).any())
+    return a, b
 
 
 LOOP = dict(n_rays=20011, seed=5, budget=1 << 40, T_thr=1e-4)

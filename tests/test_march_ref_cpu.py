@@ -114,7 +114,7 @@ def test_sparse_rays_fill_every_class_of_the_early_out():
 
 @pytest.mark.parametrize("name", ["sparse", "sparse_quarter", "sparse_wide"])
 def test_the_early_out_is_exact(name):
-    """The claim of march_slots_wave_kernel's comment: no ray the early out ends has a sample in the oracle's walk."""
+    """The claim of lat_near_occupied's comment (march.h): no ray the early out ends has a sample in the oracle's walk."""
     s, c = MR.march_set(name), MR.sparse_classes(name)
     n_skip, n_emit, n_dil = int(c.skipped.sum()), int((c.counts > 0).sum()), int(c.dilation_only.sum())
     print(f"{name}: {n_skip} of {s.n_rays} rays skipped, {n_emit} emit, {n_dil} of them kept by the dilation only")
@@ -165,6 +165,11 @@ def test_scan_sets_interleave_misses(n):
     assert bool(miss[2::3].all()) and int((r.counts[0::3] > 0).sum()) > 0.3 * n  # interleaved with hits
     assert int(r.counts[1024]) > 0 and r.total > 20 * n
     assert torch.equal(r.rays_a[:, 1], torch.cumsum(r.rays_a[:, 2], 0) - r.rays_a[:, 2])
+    if n == MR.SCAN_N_RAYS[-1]:  # what the wave march's register-held segment has to get right (render_ref)
+        dt = float(np.float32(O.lib().or_calc_dt(1.0, 0.0, s.cfg["max_samples"], s.cfg["grid"], s.cfg["scale"])))
+        straddle, leave = RR.segment_crossings([r.ts[a:a + c].numpy() for _, a, c in r.rays_a.tolist()], dt)
+        print(f"scan {n}: {straddle} rays' samples span a power of two, {leave} rays jump out of a binade")
+        assert straddle >= 1 and leave >= 1
 
 
 # ---------------------------------------------------------------- cascaded

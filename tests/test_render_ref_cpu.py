@@ -123,6 +123,19 @@ def test_zero_sets_start_below_every_binade(name):
         assert ts[0] == 0 and ts[1] == np.float32(RR.DT) and (ts != closed).any()
 
 
+@pytest.mark.parametrize("name", ["wave16", "wave64", "zero64", "blocks16", "zero16"])
+def test_wave_sets_cross_lattice_segments(name):
+    """the wave mode walks a window on one register-held segment: the sets hold windows that straddle a segment's end
+    and jumps that leave it (zero16's rays cross a dense grid: no jumps there)"""
+    s, r = RR.march_set(name), RR.march_set_ref(name)
+    assert s.cfg["cascades"] == 1 and s.cfg["esf"] == 0 and s.Ns >= RR.WAVE_NS  # the launch takes the wave mode
+    straddle, leave = RR.segment_crossings([r.ts[n::s.n_alive][:int(r.n_eff[n])].numpy() for n in range(s.n_alive)], RR.DT)
+    print(f"{name}: {straddle} rays' samples span a power of two, {leave} rays jump out of a binade")
+    assert straddle >= 1
+    if name != "zero16":
+        assert leave >= 1
+
+
 def test_flush_sets_sit_on_both_sides_of_the_flush_level():
     level = RR.STAGE - RR.FLUSH_SLACK
     f, n = RR.march_set("flush"), RR.march_set("noflush")
