@@ -25,6 +25,7 @@
 #include "field_net.h"
 #include "grid.h"
 #include "transmittance.h"
+#include "wave.h"
 
 namespace ngp {
 
@@ -933,7 +934,7 @@ __device__ __forceinline__ int colsum_exp(const _Float16* img, int nin, int nout
             a += fabsf((float)v[2]);
             a += fabsf((float)v[3]);
         }
-    for (int off = 32; off > 0; off >>= 1) a = fmaxf(a, __shfl_xor(a, off, 64));
+    a = wave_max(a);
     int e = 0;
     const float m = frexpf(a, &e);
     e = a == 0.f ? -30 : (m == 0.5f ? e - 1 : e);  // ceil(log2(a)) (a = 2^(e-1) exactly: e - 1)

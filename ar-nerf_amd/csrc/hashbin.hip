@@ -49,6 +49,7 @@
 
 #include "common.h"
 #include "grid.h"
+#include "wave.h"
 
 namespace ngp {
 
@@ -227,12 +228,7 @@ __global__ void __launch_bounds__(256) hash_scan_kernel(const int64_t* __restric
         const int64_t tile = c0 + t;
         uint32_t* p = ws.ofs + (size_t)slot * ba.tiles_cap + tile;
         const uint32_t v = tile < ntiles ? *p : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
+        const uint32_t x = wave_incl_scan(v, lane);
         if (lane == 63) wsum[w] = x;
         __syncthreads();
         uint32_t before = carry;
@@ -419,12 +415,7 @@ __global__ void __launch_bounds__(256) hash_write_kernel(const float* __restrict
             __syncthreads();
             if (t < 64) {  // exclusive scan of the tile's per-bucket counts (MODE 0, diagnostics: NBL <= 64)
                 const uint32_t h = hist[t];
-                uint32_t x = h;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t y = __shfl_up(x, o, 64);
-                    if (t >= o) x += y;
-                }
+                const uint32_t x = wave_incl_scan(h, t);
                 loff[t] = x - h;
                 if (t == 63) loff[NBL] = x;
             }

@@ -51,6 +51,7 @@
 #pragma clang fp contract(off)
 #include "field_net.h"
 #include "grid.h"
+#include "wave.h"
 
 #ifdef NGP_ENC_PAIR_MAJOR
 #define NGP_INPUT_GRAD_KERNEL field_input_grad_pm_kernel
@@ -76,7 +77,6 @@ __device__ __forceinline__ void unit_fence(float (&a)[4]) {
     asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : : "memory");
     __builtin_amdgcn_sched_barrier(0);
 }
-__device__ __forceinline__ float xor_sum(float v, int m) { return v + __shfl_xor(v, m, 64); }
 
 // One level's contribution to dL/dx01 of one sample: gx_d = fmaf(scale, acc_d, gx_d)
 __device__ __forceinline__ void level_pos_grad(const float in[3], int l, const LevelLds& lv,
@@ -162,7 +162,7 @@ __global__ void __launch_bounds__(256) NGP_INPUT_GRAD_KERNEL(
         }
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-            const float v = xor_sum(xor_sum(gx[d], 16), 32);  // (g0 + g1) + (g2 + g3)
+            const float v = wave_xor_add(wave_xor_add(gx[d], 16), 32);  // (g0 + g1) + (g2 + g3)
             if (valid && g == 0) dL_dx[3 * i + d] = v / (ga.g.xyz_max[d] - ga.g.xyz_min[d]);
         }
         if (!want_d) continue;
@@ -294,12 +294,10 @@ __global__ void __launch_bounds__(256) ray_segment_sum_kernel(const float* __res
         }
     }
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            so[d] = xor_sum(so[d], m);
-            sd[d] = xor_sum(sd[d], m);
-        }
+    for (int d = 0; d < 3; ++d) {
+        so[d] = wave_sum(so[d]);
+        sd[d] = wave_sum(sd[d]);
+    }
     if (lane < 3) {
         dL_do[3 * ray + lane] = lane == 0 ? so[0] : lane == 1 ? so[1] : so[2];
         dL_drd[3 * ray + lane] = lane == 0 ? sd[0] : lane == 1 ? sd[1] : sd[2];

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "march.h"
+#include "wave.h"
 
 namespace ngp {
 
@@ -223,8 +224,7 @@ __global__ void __launch_bounds__(64) march_count_kernel(const float* __restrict
 }
 
 // Exclusive scan of the per-ray counts -> ray-ordered rays_a + total, in one
-// 1024-lane workgroup (8192 rays = 8 elements per lane).  Wave-level
-// inclusive scan with DPP-backed __shfl_up, then a 16-wave LDS carry.
+// 1024-lane workgroup (8192 rays = 8 elements per lane): wave.h's block scan.
 __global__ void __launch_bounds__(1024) scan_rays_kernel(const int32_t* __restrict__ counts, int64_t n_rays,
                                                          int64_t* __restrict__ rays_a, int64_t* __restrict__ total) {
     __shared__ int64_t wave_sums[16];
@@ -242,26 +242,7 @@ __global__ void __launch_bounds__(1024) scan_rays_kernel(const int32_t* __restri
             v[k] = (i < n_rays) ? counts[i] : 0;
             local += v[k];
         }
-        int64_t incl = local;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int64_t y = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += y;
-        }
-        if (lane == 63) wave_sums[wid] = incl;
-        __syncthreads();
-        if (wid == 0) {
-            int64_t ws = lane < 16 ? wave_sums[lane] : 0;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const int64_t y = __shfl_up(ws, off, 64);
-                if (lane >= off) ws += y;
-            }
-            if (lane < 16) wave_sums[lane] = ws;  // inclusive over waves
-        }
-        __syncthreads();
-        const int64_t carry = carry_s;
-        int64_t run = carry + (wid > 0 ? wave_sums[wid - 1] : 0) + incl - local;
+        int64_t run = block_excl_scan_1024(local, wave_sums, &carry_s, lane, wid);
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int64_t i = base + (int64_t)tid * PER + k;
@@ -272,9 +253,7 @@ __global__ void __launch_bounds__(1024) scan_rays_kernel(const int32_t* __restri
             }
             run += v[k];
         }
-        __syncthreads();
-        if (tid == 1023) carry_s = run;
-        __syncthreads();
+        block_scan_carry_1024(wave_sums, &carry_s);
     }
     if (tid == 0) *total = carry_s;
 }

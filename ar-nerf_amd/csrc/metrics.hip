@@ -19,6 +19,7 @@
 #pragma clang fp contract(off)
 
 #include "common.h"
+#include "wave.h"
 
 namespace ngp {
 
@@ -33,12 +34,6 @@ constexpr double IM_C1 = 1e-4, IM_C2 = 9e-4;  // (0.01 L)^2, (0.03 L)^2 at data_
 struct ImWindow {
     double g[IM_K];
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(IM_THREADS) image_metrics_tile_kernel(const float* __restrict__ pred,
                                                                        const float* __restrict__ gt, int h, int w,

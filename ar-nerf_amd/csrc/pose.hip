@@ -38,6 +38,7 @@
 //                       nothing.
 #pragma clang fp contract(off)
 #include "common.h"
+#include "wave.h"
 
 namespace ngp {
 
@@ -142,8 +143,6 @@ __global__ void __launch_bounds__(256) rod_coefficients_kernel(const float* __re
     out[4 * j + 3] = rod_dB(th, s, sh);
 }
 
-__device__ __forceinline__ float pose_xor_sum(float v, int m) { return v + __shfl_xor(v, m, 64); }
-
 constexpr int POSE_THREADS = 256, POSE_WAVES = POSE_THREADS / 64;
 
 __global__ void __launch_bounds__(POSE_THREADS) pose_grad_kernel(
@@ -179,13 +178,11 @@ __global__ void __launch_bounds__(POSE_THREADS) pose_grad_kernel(
         }
     }
 #pragma unroll
-    for (int m = 32; m >= 1; m >>= 1)
+    for (int a = 0; a < 3; ++a) {
+        st[a] = wave_sum(st[a]);
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            st[a] = pose_xor_sum(st[a], m);
-#pragma unroll
-            for (int b = 0; b < 3; ++b) G[a][b] = pose_xor_sum(G[a][b], m);
-        }
+        for (int b = 0; b < 3; ++b) G[a][b] = wave_sum(G[a][b]);
+    }
     if (lane == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) {

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "march.h"
 #include "sh9.h"
+#include "wave.h"
 
 namespace ngp {
 
@@ -93,9 +94,7 @@ __global__ void __launch_bounds__(PJ_THREADS) probe_sh9_project_kernel(const flo
             for (int c = 0; c < 4; ++c) acc[4 * k + c] += Y[k] * v[c];
     }
 #pragma unroll
-    for (int a = 0; a < PJ_ACC; ++a)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[a] += __shfl_xor(acc[a], o, 64);
+    for (int a = 0; a < PJ_ACC; ++a) acc[a] = wave_sum(acc[a]);
     __shared__ float part[PJ_WAVES][PJ_ACC];
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll

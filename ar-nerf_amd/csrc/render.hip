@@ -22,6 +22,7 @@
 // reference's values bit for bit.
 #pragma clang fp contract(off)
 #include "march.h"
+#include "wave.h"
 
 namespace ngp {
 
@@ -63,17 +64,6 @@ __global__ void render_iter_kernel(int64_t* __restrict__ state, int parity, int6
     state[RS_ITERS] += 1;
 }
 
-// Inclusive prefix sum over the 64 lanes of a wave.
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
 // Block-wide append (blockDim 256, called by every thread of the block):
 // this thread's first index for `cnt` items; ONE counter atomic per block
 // (same-address atomics serialise: one per wave cost ~100 us per iteration
@@ -82,7 +72,7 @@ __device__ __forceinline__ int64_t block_append(int cnt, unsigned long long* cou
     __shared__ int wtot[4];
     __shared__ int64_t boff;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int incl = wave_incl_scan(cnt);
+    const int incl = wave_incl_scan(cnt, lane);
     if (lane == 63) wtot[w] = incl;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -111,7 +101,7 @@ __device__ __forceinline__ void block_append_k(const int (&cnt)[CRPT], int64_t (
     int incl[CRPT];
 #pragma unroll
     for (int k = 0; k < CRPT; ++k) {
-        incl[k] = wave_incl_scan(cnt[k]);
+        incl[k] = wave_incl_scan(cnt[k], lane);
         if (lane == 63) wt[k][w] = incl[k];
     }
     __syncthreads();
@@ -347,8 +337,7 @@ __global__ void __launch_bounds__(256) render_composite_kernel(const float* __re
         for (int k = 0; k < CRPT; ++k)
             if (kept[k] >= 0) alive_out[off[k]] = kept[k];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) my_total += __shfl_xor(my_total, o, 64);
+    my_total = wave_sum(my_total);
     __shared__ int wsum[4];  // one total atomic per block, not per wave
     if (lane == 0) wsum[threadIdx.x >> 6] = my_total;
     __syncthreads();

@@ -1,5 +1,5 @@
 // Transmittance of a row over one 64-sample chunk: shared by the compositing
-// kernels (train.hip), the round-2 list (chunk_segments_kernel) and the
+// kernels (loss.hip), the round-2 list (chunk_segments_kernel, rows.hip) and the
 // per-row field forward (field.hip), so every evaluation rule sees exactly
 // the composite's termination.
 #pragma once

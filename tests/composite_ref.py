@@ -1,5 +1,5 @@
 """fp64 per-sample references, rounding bounds and designed input sets for the
-compositing kernels and the fused NeRF loss: ngp_composite_loss (train.hip),
+compositing kernels and the fused NeRF loss: ngp_composite_loss (loss.hip),
 ngp_composite_train_fw / _bw and ngp_composite_test_fw (composite.hip) and
 ngp_nerf_loss_fw / _bw.  A plain helper module (not a conftest), like
 hash_ref.py: test_composite_ref_cpu.py shows on the CPU that the references
@@ -45,7 +45,7 @@ count), n_active = min(K + 1, N): the samples that carry gradient.
   of additions a term can pass through -- the only thing that differs
   between the paths:
     serial  (composite.hip, readlane left folds)         depth = n
-    tree    (train.hip: 6-level wave sums / Hillis-Steele
+    tree    (loss.hip: wave.h's 6-level wave sums / Hillis-Steele
              scans per 64-sample chunk + one carry per chunk) depth = 6 + ceil(n / 64)
     test    (composite_test_kernel, a serial loop onto a
              non-zero base: the base counts as a term)    depth = n + 1

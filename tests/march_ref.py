@@ -149,6 +149,7 @@ D_CLASSES = (0.1, 1.0, 10.0)
 ROOM_MAX_SAMPLES = (1, 63, 64, 65, 100)
 ROOM_N_RAYS = (1, 3, 4, 5)
 SCAN_N_RAYS = (1025, 2500)
+SCAN_TILE_N_RAYS = 8193  # 1024 x 8 + 1: the smallest launch with a second tile of the 1024-thread block scan
 CASCADED_N_RAYS = (1, 15, 16, 17, 63, 65, 300)
 SEEDS = {"sparse": 1, "sparse_quarter": 1, "sparse_wide": 2}  # chosen so that test_march_ref_cpu.py's conditions hold
 
@@ -217,8 +218,8 @@ def march_set(name, *arg):
       room, ms, n     dense bitfield, max_samples ms in ROOM_MAX_SAMPLES, the first n in ROOM_N_RAYS of five rays
                       with |d| = 0.25: rays 0, 2, 3 cross more than ms lattice points, rays 1 and 4 fewer (with
                       unit directions no chord of the box holds more than ms steps of sqrt3 / ms: no cut at all)
-      scan, n         n in SCAN_N_RAYS rays on rand0.2, every third one missing the box (ray 1024, the first past a lane-per-ray
-                      scan, hits)
+      scan, n         n in SCAN_N_RAYS (or SCAN_TILE_N_RAYS) rays on rand0.2, every third one missing the box (ray 1024,
+                      the first past a lane-per-ray scan, hits)
       cascaded, n     render_ref.CASCADED (3 cascades, scale 2, exp step): sparse whole blocks in cascades 1 and 2, a
                       few single cells in cascade 0; the first n in CASCADED_N_RAYS of 300 rays"""
     if name in ("sparse", "sparse_quarter", "sparse_wide"):

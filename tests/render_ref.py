@@ -30,15 +30,15 @@ from capi import C
 # ------------------------------------------------- mirrored kernel constants
 STATE_WORDS = C["NGP_RENDER_STATE_WORDS"]
 RS_ALIVE0, RS_ALIVE1, RS_SAMPLES, RS_NS, RS_ACTIVE, RS_VALID, RS_TOTAL, RS_ITERS = range(8)  # march.h:535-536
-NS_MAX = 64                # render.hip:57   N_samples = min(N_rays // N_alive, 64)
-BLOCK = 256                # render.hip:234  __launch_bounds__(256) of every loop kernel
-WAVE_RAYS = 4              # render.hip:180  rays per block per trip of the wave-per-ray mode (one per wave)
-CRPT = 4                   # render.hip:100  rays per thread per composite pass
-WAVE_NS = 16               # render.hip:146  N_samples from which a SIMPLE march runs wave-per-ray
-STAGE = 2048               # render.hip:147  staged sample indices per block
-FLUSH_SLACK = 4 * 64       # render.hip:228  flush when nst > STAGE - 4 * 64
-MARCH_BLOCKS = 2048        # render.hip:383  grid cap of the march
-COMPOSITE_BLOCKS = 1024    # render.hip:440  grid cap of the composite
+NS_MAX = 64                # render.hip:58   N_samples = min(N_rays // N_alive, 64)
+BLOCK = 256                # render.hip:224  __launch_bounds__(256) of every loop kernel
+WAVE_RAYS = 4              # render.hip:170  rays per block per trip of the wave-per-ray mode (one per wave)
+CRPT = 4                   # render.hip:90   rays per thread per composite pass
+WAVE_NS = 16               # render.hip:136  N_samples from which a SIMPLE march runs wave-per-ray
+STAGE = 2048               # render.hip:137  staged sample indices per block
+FLUSH_SLACK = 4 * 64       # render.hip:218  flush when nst > STAGE - 4 * 64
+MARCH_BLOCKS = 2048        # render.hip:372  grid cap of the march
+COMPOSITE_BLOCKS = 1024    # render.hip:429  grid cap of the composite
 LSEG = 32                  # march.h:286    lattice segments per ray
 NEAR = 0.01                # models/rendering.py NEAR_DISTANCE
 

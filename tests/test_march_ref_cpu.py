@@ -155,7 +155,7 @@ def test_room_rays_are_cut_by_max_samples(max_samples):
 
 
 # -------------------------------------------------------------------- scan
-@pytest.mark.parametrize("n", MR.SCAN_N_RAYS)
+@pytest.mark.parametrize("n", MR.SCAN_N_RAYS + (MR.SCAN_TILE_N_RAYS,))
 def test_scan_sets_interleave_misses(n):
     s, r = MR.march_set("scan", n), MR.march_set_ref("scan", n)
     miss = s.ht[:, 0] < 0

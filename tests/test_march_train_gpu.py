@@ -236,14 +236,18 @@ def test_early_out_classes_on_the_device(on_device):
 
 
 # ----------------------------------------------------------------- two pass
-@pytest.mark.parametrize("key", [k for k in SETS if k[0] in ("sparse", "scan", "cascaded")], ids=_id)
+@pytest.mark.parametrize("key", [k for k in SETS if k[0] in ("sparse", "scan", "cascaded")]
+                         + [("scan", MR.SCAN_TILE_N_RAYS)], ids=_id)
 def test_two_pass_path_bit_for_bit(key, on_device):
     """vren.march_train_count / march_train_write (march_count_kernel, scan_rays_kernel, march_write_kernel; both
     template instantiations over the sets): counts, rays_a, total and the four outputs equal the oracle's and the
-    slot path's bit for bit, with and without the summary on the slot side; the padding is untouched."""
+    slot path's bit for bit, with and without the summary on the slot side; the padding is untouched.  The starts
+    in rays_a are the exclusive cumsum of the counts (SCAN_TILE_N_RAYS: across the block scan's tile carry)."""
     s, ref, D = MR.march_set(*key), MR.march_set_ref(*key), on_device(key)
     scan, res = _two_pass(s, D)
     assert torch.equal(scan.counts.cpu(), ref.counts) and torch.equal(scan.rays_a.cpu(), ref.rays_a)
+    cnt = scan.counts.cpu().long()
+    assert torch.equal(scan.rays_a[:, 1].cpu(), torch.cumsum(cnt, 0) - cnt) and scan.total == int(cnt.sum())
     assert scan.total == ref.total
     _check_samples(res, ref)
     for how in ("kernel", "none"):

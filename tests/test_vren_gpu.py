@@ -442,7 +442,7 @@ def test_chunk_segments_equals_counts_then_segments(n_rows, first, last):
         assert 0 < int(tot_ref) < int(N.sum())
 
 
-@pytest.mark.parametrize("n_rows", [1, 100, 8192, 70000])
+@pytest.mark.parametrize("n_rows", [1, 63, 64, 65, 100, 8192, 8193, 70000])
 def test_rays_nonempty_lists_rows_and_zeroes_empty_counts(n_rows):
     """ngp_rays_nonempty: the rows with N > 0 in ascending order and their
     count; rest[r] = 0 for every empty row, the others untouched (the row
