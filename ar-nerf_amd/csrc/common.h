@@ -11,6 +11,8 @@
     do {                           \
         if (!(cond)) return NGP_EINVAL; \
     } while (0)
+// a colour mode outside NGP_RGB_* is refused before anything else is looked at
+#define NGP_CHECK_RGB_ACT(a) NGP_CHECK_ARG((a) >= NGP_RGB_SIGMOID && (a) <= NGP_RGB_RELU)
 
 static inline int ngp_launch_status() {
     hipError_t e = hipGetLastError();

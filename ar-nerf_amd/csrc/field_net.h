@@ -19,18 +19,6 @@ constexpr int R32 = 40, R64 = 72;
 constexpr int SW1 = 0, SW2 = SW1 + 64 * R32, SW3 = SW2 + 16 * R64, SW4 = SW3 + 64 * R32, SW5 = SW4 + 64 * R64,
               SWF = SW5 + 16 * R64;
 
-// K permutations matching the register re-pack of accumulator tiles:
-// step q, lane group g, element j <- hidden unit 32q + (j<4 ? 4g+j : 16+4g+j-4)
-__device__ __forceinline__ int P64(int kp) {
-    const int q = kp >> 5, g = (kp >> 3) & 3, j = kp & 7;
-    return 32 * q + (j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4));
-}
-// colour-net input c = [SH(16), h(16)]: element j <- j<4 ? SH[4g+j] : h[4g+j-4]
-__device__ __forceinline__ int P32(int kp) {
-    const int g = kp >> 3, j = kp & 7;
-    return j < 4 ? 4 * g + j : 16 + 4 * g + (j - 4);
-}
-
 __device__ __forceinline__ f4 mfma32(h8 a, h8 b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
 // tcnn SphericalHarmonics degree 4 of (d/|d|+1)/2 (models/networks.py:144-145),
@@ -83,38 +71,21 @@ __device__ __forceinline__ h4 relu_h(f4 c) {
 __device__ __forceinline__ h4 to_h(f4 c) { return h4{(_Float16)c[0], (_Float16)c[1], (_Float16)c[2], (_Float16)c[3]}; }
 __device__ __forceinline__ h8 lds8(const _Float16* p) { return *reinterpret_cast<const h8*>(p); }
 
-// Stage the raw fp16 MLP buffer (row-major, 20 KB) into LDS with coalesced
-// 16-byte loads; the permuted / transposed images are then built LDS->LDS
-// (strided 2-byte global reads there were latency-bound: one wave per SIMD).
-__device__ __forceinline__ void stage_raw_weights(const _Float16* __restrict__ mlp, _Float16* raw) {
-    const h8* src = reinterpret_cast<const h8*>(mlp);
-    h8* dst = reinterpret_cast<h8*>(raw);
-    for (int i = threadIdx.x; i < NGP_MLP_PARAMS / 8; i += blockDim.x) dst[i] = src[i];
-}
-
-// Build the forward weight image (permuted columns, padded rows) in LDS from
-// the staged raw buffer.
-__device__ __forceinline__ void load_fwd_weights(const _Float16* __restrict__ mlp, _Float16* sw, bool color) {
-    const int t = threadIdx.x, nt = blockDim.x;
-    for (int i = t; i < 64 * 32; i += nt) sw[SW1 + (i >> 5) * R32 + (i & 31)] = mlp[OW1 + i];
-    for (int i = t; i < 16 * 64; i += nt) sw[SW2 + (i >> 6) * R64 + (i & 63)] = mlp[OW2 + (i >> 6) * 64 + P64(i & 63)];
-    if (!color) return;
-    for (int i = t; i < 64 * 32; i += nt) sw[SW3 + (i >> 5) * R32 + (i & 31)] = mlp[OW3 + (i >> 5) * 32 + P32(i & 31)];
-    for (int i = t; i < 64 * 64; i += nt) sw[SW4 + (i >> 6) * R64 + (i & 63)] = mlp[OW4 + (i >> 6) * 64 + P64(i & 63)];
-    for (int i = t; i < 16 * 64; i += nt) sw[SW5 + (i >> 6) * R64 + (i & 63)] = mlp[OW5 + (i >> 6) * 64 + P64(i & 63)];
-}
-
-// Inverses of P64 / P32: weight column i -> its position in the permuted row.
+// K permutations matching the register re-pack of accumulator tiles, as the
+// position of weight column i in the permuted row.  P64: position 32q + 8g + j
+// (step q, lane group g, element j) holds hidden unit 32q + (j<4 ? 4g+j :
+// 16+4g+j-4); P32, the colour-net input [SH(16), h(16)]: position 8g + j holds
+// j<4 ? SH[4g+j] : h[4g+j-4].
 __device__ __forceinline__ int P64inv(int i) {
     const int q = i >> 5, r = i & 31;
     return 32 * q + (r < 16 ? 8 * (r >> 2) + (r & 3) : 8 * ((r - 16) >> 2) + 4 + (r & 3));
 }
 __device__ __forceinline__ int P32inv(int i) { return i < 16 ? 8 * (i >> 2) + (i & 3) : 8 * ((i - 16) >> 2) + 4 + (i & 3); }
 
-// The forward weight image built straight from global memory: coalesced
-// 16-byte loads of the row-major buffer, each half scattered to its permuted
-// LDS position (8 consecutive halfs share one row) -- no 20 KB raw staging
-// buffer, so the MLP-only forward fits more blocks per CU.
+// The forward weight image (permuted columns, padded rows) built straight from
+// global memory: coalesced 16-byte loads of the row-major buffer, each half
+// scattered to its permuted LDS position (8 consecutive halfs share one row);
+// the image is all the LDS a forward block needs.
 // the 8 halfs v of the row-major buffer at flat index i0 (a multiple of 8) into
 // the forward image: their row, each column at its permuted position
 __device__ __forceinline__ void place_fwd8(int i0, h8 v, _Float16* sw) {

@@ -1,8 +1,9 @@
 // The hash grid's level table and the one statement of its per-level
 // arithmetic (tcnn GridEncoding: pos_fract, the trilinear weights, grid_index),
-// which every kernel that touches a level calls: the forward gathers and the
-// coarse scatter (field.hip), the binned backward (hashbin.hip) and the input
-// gradients (normal.hip, inputgrad.hip).  What is bit-exact against the oracle
+// which every kernel that touches a level calls: the forward gathers (level.h,
+// for field.hip), the coarse scatter (hash_bwd.hip), the binned backward
+// (hashbin.hip) and the input gradients (normal.hip, inputgrad.hip).  What is
+// bit-exact against the oracle
 // (or_* in oracle/vren_oracle.c) is so because it is written here once.
 #pragma once
 #pragma clang fp contract(off)

@@ -1,5 +1,5 @@
 // Binned hash-table backward: dL/dtable without per-sample memory-side
-// atomics.  Same result as hash_bwd_kernel (field.hip) / tcnn's
+// atomics.  Same result as hash_bwd_kernel (hash_bwd.hip) / tcnn's
 // kernel_grid_backward (the `params.grad` that models/networks.py's
 // xyz_encoder receives), up to fp32 rounding/summation order.
 //

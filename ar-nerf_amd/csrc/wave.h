@@ -12,8 +12,8 @@
 // Value types in use: float, double, int32_t, uint32_t, int64_t, unsigned
 // long long.  Not routed through here, on purpose: the product scan of
 // transmittance.h, the lane-group sum of inputgrad.hip ((g0+g1)+(g2+g3), two
-// wave_xor_add steps in its own order), field.hip's DPP / permlane
-// reductions, the stride-4 run logic of field.hip and hashbin.hip, and
+// wave_xor_add steps in its own order), field_bwd.hip's DPP / permlane
+// reductions, the stride-4 run logic of hash_bwd.hip and hashbin.hip, and
 // composite.hip's serial readlane folds.
 #pragma once
 #include "common.h"

@@ -302,7 +302,7 @@ class _RoundGrad16(torch.autograd.Function):
     in fp16 (the pre-activation gradient of every layer, ReLU' applied), at a
     power-of-two scale that keeps it in fp16's normal range -- a power-of-two
     scale is exact, so the rounding is the mantissa's alone.  The product's
-    MLP backward (field.hip field_bwd_mlp_coop_kernel) rounds at the same five
+    MLP backward (field_bwd.hip field_bwd_mlp_coop_kernel) rounds at the same five
     points with per-sample power-of-two scales."""
 
     @staticmethod

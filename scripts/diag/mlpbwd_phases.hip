@@ -19,7 +19,8 @@ __device__ unsigned long long g_bwd_edges[1024 * 4];
     do {                                                                                              \
         if (threadIdx.x == 0 && blockIdx.x < 1024) g_bwd_edges[blockIdx.x * 4 + (k)] = wall_clock64(); \
     } while (0)
-#include "../../ar-nerf_amd/csrc/field.hip"
+#include "../../ar-nerf_amd/csrc/field_bwd.hip"
+#include "../../ar-nerf_amd/csrc/hash_bwd.hip"
 #include "../../ar-nerf_amd/csrc/host.hip"
 
 extern "C" int ngp_diag_bwd_stamps(unsigned long long* host, unsigned long long* edges, int clear) {

@@ -1,5 +1,5 @@
 """Exact input sets and a plain fp64 reference for the MLP backward
-(field.hip field_bwd_mlp_coop_kernel, C ABI ngp_field_backward_mlp_act).  CPU
+(field_bwd.hip field_bwd_mlp_coop_kernel, C ABI ngp_field_backward_mlp_act).  CPU
 only, numpy fp64.
 
 The kernel stores the forward in fp16, the gradient chain in fp16 times a

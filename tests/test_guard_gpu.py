@@ -50,6 +50,58 @@ def test_count_past_capacity_is_counted_not_silent():
     assert L.ngp_guard_hits() == 0
 
 
+def test_backward_units_count_in_their_own_guard_words():
+    """The guard counter is per translation unit: the MLP backward
+    (field_bwd.hip) and the atomic hash backward (hash_bwd.hip) each clamp a
+    device count 1000 past the capacity, count it in their own word, and write
+    what the call with the exact count writes -- dL/denc bit for bit, the atomic
+    table gradient of levels 0..2 within test_hashbin_gpu.py's (cnt + 16) u mag
+    of the fp64 scatter."""
+    import hash_ref as R
+    L, K, s = vren.lib(), HG._K(), vren._stream()
+    assert L.ngp_guard_reset() == 0 and L.ngp_guard_hits() == 0
+    grid = HG.HashGrid(0.5)
+    p16 = HG.init_params(grid, seed=1, table_init=1.0).half()
+    n, lo, hi = 100, 0, 3
+    xyz, d = _inputs(n)
+    g = torch.Generator().manual_seed(5)
+    dsig, drgb = torch.randn(n, generator=g).cuda(), torch.randn(n, 3, generator=g).cuda()
+    exact, past = (torch.tensor([c], dtype=torch.int64, device="cuda") for c in (n, n + 1000))
+    _, _, enc, _ = HG.field_forward(xyz, d, grid, p16)
+    try:
+        def mlp_bwd(n_dev):
+            denc, gm = torch.zeros(n, 32, device="cuda"), torch.zeros(HG.MLP_PARAMS, device="cuda")
+            K.ngp_field_backward_mlp_act(d, n, n_dev, None, enc, 0, p16, dsig, drgb, denc, gm, HG.RGB_SIGMOID, s)
+            torch.cuda.synchronize()
+            return denc
+
+        def hash_bwd(n_dev, denc):
+            gt = torch.zeros(2 * grid.n_entries, device="cuda")
+            K.ngp_hash_backward_levels(xyz, n, n_dev, None, grid.desc, denc, gt, lo, hi, s)
+            torch.cuda.synchronize()
+            return gt
+
+        denc0 = mlp_bwd(exact)
+        gt0 = hash_bwd(exact, denc0)
+        assert L.ngp_guard_hits() == 0 and float(denc0.abs().max()) > 0
+        denc1 = mlp_bwd(past)
+        h1 = int(L.ngp_guard_hits())
+        assert h1 >= 1, "the MLP backward's clamp must be counted"
+        assert torch.equal(denc0, denc1)
+        gt1 = hash_bwd(past, denc0)
+        assert int(L.ngp_guard_hits()) >= h1 + 1, "the hash backward's clamp must be counted"
+        sp = R.spec(0.5)
+        ref, mag, cnt = R.scatter_ref64(sp, xyz.cpu(), *R.box(0.5), denc0.cpu(), levels=range(lo, hi))
+        bound = R.scatter_bound(sp, ref, mag, cnt)
+        for what, gt in (("exact count", gt0), ("count past the capacity", gt1)):
+            ratios = R.level_ratios(sp, (gt.cpu().double() - ref).abs(), bound)
+            print(f"atomic levels [{lo}, {hi}), {what}: worst err/bound {max(ratios):.3f}")
+            assert float(mag.max()) > 0 and max(ratios) <= 1.0, (what, ratios)
+    finally:
+        assert L.ngp_guard_reset() == 0
+    assert L.ngp_guard_hits() == 0
+
+
 def test_trainer_overflow_of_the_round2_list_is_counted():
     """The row forward's round-2 list bounded by its capacity (field.hip,
     ngp_field_forward_first_pre): a list smaller than the rows' remaining

@@ -1,4 +1,4 @@
-"""The hash-table backward -- per-sample atomics (field.hip) and the binned
+"""The hash-table backward -- per-sample atomics (hash_bwd.hip) and the binned
 path (hashbin.hip) -- and the FusedAdam folded into the binned accumulation,
 each held to an fp64 reference outside the product, entry by entry and per
 level: tests/hash_ref.py's scatter_ref64 / adam_ref64 (built from the oracle's

@@ -1,4 +1,4 @@
-"""The MLP backward (field.hip field_bwd_mlp_coop_kernel, through the C ABI's
+"""The MLP backward (field_bwd.hip field_bwd_mlp_coop_kernel, through the C ABI's
 ngp_field_backward_mlp_act) pinned with two instruments a tolerance cannot
 replace:
 
@@ -37,7 +37,7 @@ import vren
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-# field.hip's launch geometry, mirrored: CW waves x 16 rows per block iteration, and the block's LDS
+# field_bwd.hip's launch geometry, mirrored: CW waves x 16 rows per block iteration, and the block's LDS
 CW = 8
 _R32, _R64, _RT16, _RT64 = 40, 72, 20, 68
 _SWF = 64 * _R32 + 16 * _R64 + 64 * _R32 + 64 * _R64 + 16 * _R64               # forward weight image

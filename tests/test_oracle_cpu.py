@@ -185,7 +185,7 @@ def test_grid_encode_fp32_vs_half_fma_accumulation():
 
 def test_mlp_weight_gradient_operand_rounding():
     """The MLP weight gradients dW = sum_s G[o][s] H[i][s] take fp16 operands
-    on the GPU (field.hip field_bwd_mlp_coop_kernel, tcnn's precision): each
+    on the GPU (field_bwd.hip field_bwd_mlp_coop_kernel, tcnn's precision): each
     sample's gradient column is rounded to fp16 at its own power-of-two scale
     (largest |g| of the sample in [2^13, 2^14)), then re-scaled exactly to the
     128-sample block's common scale (factors <= 1: a second rounding only
