@@ -290,6 +290,37 @@ def render_insert_sg(model, c2w, directions, H, W, rect, bbox, normals, obj_dept
     return rr.render_rect(c2w, rect)
 
 
+@torch.no_grad()
+def render_insert_sg_shadow(model, c2w, directions, H, W, rect, bbox, normals, obj_depth, lSGs, shadow, scale,
+                            model_pos, rot_inv=None, self_shadow=True, gen_shadow=True, **kwargs):
+    """render_insert_sg with the SSDF soft shadows of an SG-lit frame
+    (insert/sg_shadow.py; sg_shadow.SGShadow `shadow`) on the
+    cached InsertRenderer: the self-shadow decay of the object's pixels
+    (self_shadow; main.py:558-567) feeds the shade, the rectangle is rendered,
+    and the cast shadow over the whole screen's surface points (gen_shadow;
+    main.py:662-672) is blurred 3 x 3 and multiplied into a NEW image: the
+    canvases stay unshadowed, as the reference's last_rgb does.  scale: the
+    model's radius; model_pos (3); rot_inv (3,3) or None -- the lights are
+    given unrotated and rotated here for the cast pass (main.py:496-499).
+    Returns render_insert_sg's canvases and, with gen_shadow, `shadowed`
+    (H,W,3), a view of the renderer's buffer.  A `decay` in kwargs is used as
+    given when self_shadow is off."""
+    shade = {k: kwargs.pop(k) for k in ('metal', 'rough', 'albedo', 'decay') if k in kwargs}
+    shade['clamp01'] = kwargs.pop('clamp01', not kwargs.get('output_radiance', False))
+    rr = _insert_renderer(model, directions, H, W, kwargs)
+    if self_shadow:
+        shade['decay'] = rr.self_shadow_decay(c2w, bbox, obj_depth, shadow, lSGs, scale, model_pos, rot_inv)
+    rr.shade_sg(c2w, bbox, normals, obj_depth, lSGs, **shade)
+    out = rr.render_rect(c2w, rect)
+    if gen_shadow:
+        lights = lSGs
+        if rot_inv is not None:
+            lights = lSGs.clone()
+            lights[:, :3] = (rot_inv @ lights[:, :3].T).T
+        out['shadowed'] = rr.cast_shadow(shadow, lights, scale, model_pos, rot_inv)
+    return out
+
+
 def __render_rays_train(model, rays_o, rays_d, hits_t, **kwargs):
     """models/rendering.py:255-298."""
     exp_step_factor = kwargs.get('exp_step_factor', 0.)

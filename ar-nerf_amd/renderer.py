@@ -301,6 +301,12 @@ class InsertRenderer(TestRenderer):
         self.rect = torch.zeros(4, dtype=torch.int32, device=dev)  # (hs, ws, hl, wl): graph A reads it, the kernel clamps it
         self._rect_host = torch.zeros(4, dtype=torch.int32).pin_memory()
         self.header = torch.zeros(HEADER_WORDS, dtype=torch.int64, device=dev)
+        # the shadow steps' buffers: the cast-shadow factor of every pixel's surface point, the
+        # shadowed copy of frame_rgb (the canvas itself stays unshadowed), and the (H*W, L) self-shadow decay,
+        # which self_shadow_decay sizes for the frame's number of lights
+        self.frame_factor = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.frame_shadowed = torch.zeros(n, 3, dtype=torch.float32, device=dev)
+        self.decay = None
 
     # ------------------------------------------------------------ pieces
     def _begin(self):
@@ -377,6 +383,38 @@ class InsertRenderer(TestRenderer):
         return shading.sg_shade(self.H, self.W, self._dirs, self._pose, bbox, normals, self.obj_depth, lSGs,
                                 metal=metal, rough=rough, albedo=albedo, decay=decay, clamp01=clamp01,
                                 out=self.obj_rgb)
+
+    @torch.no_grad()
+    def self_shadow_decay(self, c2w, bbox, obj_depth, shadow, lSGs, scale, model_pos, rot_inv=None):
+        """The frame's self-shadow decay on the device (sg_shadow.SGShadow.frame_decay):
+        obj_depth (H,W) is written to the renderer's buffer and, for every pixel the object covers inside the
+        model's box bbox, row p of the renderer's persistent (H*W, L) decay buffer is written (the buffer is
+        reallocated when L changes and starts as ones; sg_shade reads covered rows only).  scale: the
+        model's radius; model_pos (3); rot_inv (3,3) or None.  Returns the buffer: shade_sg(..., decay=it)
+        follows.  Outside the captured graphs."""
+        import shading
+        self._pose.copy_(c2w.reshape(3, 4))
+        shading._arg("obj_depth", obj_depth, torch.float32, self.n_rays, f"(H,W) = ({self.H},{self.W})")
+        if obj_depth.data_ptr() != self.obj_depth.data_ptr():
+            self.obj_depth.copy_(obj_depth.reshape(self.obj_depth.shape))
+        import sg_shadow
+        L = sg_shadow._lights_arg(lSGs)
+        buf = self.decay
+        if buf is None or buf.shape[1] != L:
+            buf = self.decay = torch.ones(self.n_rays, L, dtype=torch.float32, device=self._pose.device)
+        return shadow.frame_decay(self.H, self.W, self._dirs, self._pose, bbox, self.obj_depth, scale, model_pos,
+                                  lSGs, buf, rot_inv)
+
+    @torch.no_grad()
+    def cast_shadow(self, shadow, lSGs, scale, model_pos, rot_inv=None):
+        """The cast shadow of the frame the canvases hold (ssdf_shadow, main.py:492-519): the factor of
+        every surface point of frame_pts (lSGs (L,7) with axes already rotated where rot_inv is given) into
+        the frame_factor buffer, then frame_rgb times its 3 x 3 blur into the frame_shadowed buffer, which
+        is returned as (H,W,3).  Eager, outside the captured graphs; frame_rgb / frame_depth / frame_pts
+        keep their bits (later frames re-render rectangles of them)."""
+        import sg_shadow
+        shadow.calc_shadow_factor(scale, self.frame_pts, model_pos, lSGs, rot_inv, out=self.frame_factor)
+        return sg_shadow.shadow_apply(self.frame_rgb, self.frame_factor, self.H, self.W, out=self.frame_shadowed)
 
     def render_frame(self, c2w, obj_rgb=None, obj_depth=None):
         """render_rect over the whole screen (the app's frame after a camera move)."""

@@ -12,8 +12,9 @@ sg_shade_torch  the same result from torch ops over (pixels, L) temporaries,
 A pixel is covered when it lies in the model's box `bbox` = (hs, ws, hl, wl)
 and obj_depth > 1e-6 (an fp32 compare); every other pixel of the frame is 0.
 A covered pixel with a zero normal is out of contract (0/0, as in the
-reference).  Not here: the SH / neural-BRDF shade, the shadow passes, tone
-mapping, and computing the self-shadow `decay` itself.
+reference).  The self-shadow `decay` and the SSDF cast shadow of an SG-lit frame
+are sg_shadow.py's.  Not here: the SH / neural-BRDF shade, the
+SH path's shadow_field and the raster shadow_cast, tone mapping.
 """
 from __future__ import annotations
 

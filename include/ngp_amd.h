@@ -355,6 +355,72 @@ int ngp_sg_shade(const int32_t* bbox, int64_t H, int64_t W, const float* directi
                  const float* albedo, int albedo_rows, const float* metal_map, float metal, const float* rough_map,
                  float rough, int clamp01, float* obj_rgb, void* stream);
 
+/* ---- SSDF soft shadows for insertion frames --------------
+ * The two calls an SG-lit frame of the insertion app makes into
+ * insert/sg_shadow.py: the self-shadow decay of every light per object pixel
+ * (calc_self_shadow_light_dacay; what ngp_sg_shade takes as `decay`) and the
+ * cast-shadow factor of every surface point of the screen
+ * (calc_shadow_factor), then the 3 x 3 blur and multiply of ssdf_shadow
+ * (main.py:503-519).  fp32, no atomics; every value is independent of the
+ * launch shape (components summed ascending, lights summed ascending in one
+ * thread).  Data, as the app loads it: coeff (G,G,G,C), the PCA coefficient
+ * volume as stored (the point's x indexes the first axis); components
+ * (C,env_h,env_w) and mean (env_h,env_w); fh_tab (n_lambda,n_theta).
+ * 1 <= C <= NGP_SSDF_MAX_COMPONENTS, G >= 2, n_lights >= 1.
+ * Out of contract, as in the reference: an axis component outside [-1,1], a
+ * sharpness of 0, a colour channel whose summed hemisphere integral is 0. */
+#define NGP_SSDF_MAX_COMPONENTS 128
+#define NGP_SSDF_LIGHT_TILE 32
+/* floats per light of the light workspace; the workspace holds
+ * n_lights * NGP_SSDF_LIGHT_WORDS + 4 floats: per light [0,C) the components
+ * sampled at the light's direction ([C,128) zero), [128] the mean there,
+ * [129] the table row coordinate (log10|lambda + 1e-6| - 1.5) / 2.5, [130]
+ * fh_n = 2 pi / lambda (1 - exp(-lambda)), [131..133] the rgb amplitude,
+ * [134..135] the light's sample position (x, y); then inte_L (3 floats, sum of 2 pi amp / lambda (1 -
+ * exp(-lambda)), lights ascending) and a 0. */
+#define NGP_SSDF_LIGHT_WORDS 136
+/* The per-light pre-pass (one block).  lSGs (n_lights,7) = axis, sharpness,
+ * rgb amplitude; rot_inv: null, or a (3,3) matrix applied to every axis first
+ * (calc_self_shadow_light_dacay rotates its lights, calc_shadow_factor takes
+ * them rotated).  phi = acos(a.y), theta = atan2(a.z, a.x); the images are
+ * sampled at (x = theta/pi, y = phi/pi*2 - 1): bilinear, pixel centres
+ * (align_corners false), border padding. */
+int ngp_sg_shadow_lights(const float* lSGs, int n_lights, const float* rot_inv, const float* components,
+                         const float* mean, int n_components, int env_h, int env_w, float* light_ws, void* stream);
+/* The hot path over pts (n_points,3).  q = rot_inv (p - model_pos) / scale /
+ * vol_range (rot_inv null: none), dis = max(|q|, 1), q /= dis, delta =
+ * (asin(1/vol_range) - asin(1/(dis vol_range))) angle_decay_fac; the volume is
+ * sampled at q (trilinear, corners at -1 and 1, border padding); per light
+ * ssdf = clip(pca . comp + mean + delta, -pi/2, pi/2) and fh = fh_tab at
+ * (x = ssdf/(pi/2), y = the light's row coordinate) as the images above.
+ * decay (n_points,n_lights), nullable: pow(clip(|fh / fh_n|, 0, 1),
+ * self_shadow_pow).  factor (n_points), nullable: pow(0.2989 r + 0.5870 g +
+ * 0.1140 b, shadow_pow) of clip(|sum_l fh amp / inte_L|, 0, 1).  One of the
+ * two at least; either alone has the bits it has beside the other.  Nothing
+ * else reaches memory.  n_points == 0 is a no-op. */
+int ngp_sg_shadow_points(const float* pts, int64_t n_points, const float* model_pos, const float* rot_inv,
+                         float scale, const float* coeff, int grid_size, int n_components, float vol_range,
+                         float angle_decay_fac, const float* light_ws, int n_lights, const float* fh_tab,
+                         int n_lambda, int n_theta, float shadow_pow, float self_shadow_pow, float* factor,
+                         float* decay, void* stream);
+/* The decay over a frame: for every pixel p inside bbox (device int32[4] =
+ * (hs, ws, hl, wl), clamped like ngp_sg_shade's) with obj_depth[p] > 1e-6
+ * (fp32 compare), the point pose[:,3] + obj_depth[p] * normalize(ray
+ * direction) (main.py:551-561; directions (H*W,3), pose (3,4), no epsilon)
+ * goes through the device function of ngp_sg_shadow_points and row p of decay
+ * (H*W,n_lights) is written.  Rows of other pixels keep their bits. */
+int ngp_sg_shadow_frame_decay(const int32_t* bbox, int64_t H, int64_t W, const float* directions, const float* pose,
+                              const float* obj_depth, const float* model_pos, const float* rot_inv, float scale,
+                              const float* coeff, int grid_size, int n_components, float vol_range,
+                              float angle_decay_fac, const float* light_ws, int n_lights, const float* fh_tab,
+                              int n_lambda, int n_theta, float self_shadow_pow, float* decay, void* stream);
+/* out_rgb[p] = frame_rgb[p] * blur(factor)[p]: the 3 x 3 Gaussian of sigma
+ * 0.8 (1-D weights exp(-0.5 (x/0.8)^2) normalised over x = -1, 0, 1, the 2-D
+ * kernel their outer product), reflect padding; H, W >= 2.  frame_rgb,
+ * out_rgb (H*W,3), factor (H*W); frame_rgb and factor are only read; one
+ * writer per pixel. */
+int ngp_shadow_apply(const float* frame_rgb, const float* factor, int64_t H, int64_t W, float* out_rgb, void* stream);
+
 /* ------------------------------------------------------- light probes */
 /* The insertion app's light probes (insert/main.py:306-407): R rays from each
  * of P scene points, the global light blended in behind them as an SH9
