@@ -27,6 +27,7 @@
 // Every value is a function of its own point and the lights alone: no atomics,
 // fixed summation orders, nothing depends on the launch shape.
 #pragma clang fp contract(off)
+#include "bilinear.h"
 #include "insert.h"
 #include "march.h"
 
@@ -49,25 +50,6 @@ static_assert(SS_TILE == 32 && SS_PTS == 64, "the 4 x 2 thread blocks below cove
 
 constexpr float SS_PI = 3.14159265358979323846f;
 constexpr float SS_HALF_PI = 1.57079632679489661923f;
-
-// F.grid_sample(img (h,w), (x,y), bilinear, padding_mode="border", align_corners=False) of one image
-__device__ __forceinline__ float bilinear_border(const float* __restrict__ img, int h, int w, float x, float y) {
-    float ix = ((x + 1.f) * (float)w - 1.f) / 2.f;
-    float iy = ((y + 1.f) * (float)h - 1.f) / 2.f;
-    ix = fminf(fmaxf(ix, 0.f), (float)(w - 1));  // (a NaN coordinate lands on 0: no index leaves the image)
-    iy = fminf(fmaxf(iy, 0.f), (float)(h - 1));
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);  // (past the edge the weight is 0)
-    const float wx1 = ix - fx, wx0 = (fx + 1.f) - ix, wy1 = iy - fy, wy0 = (fy + 1.f) - iy;
-    const float* r0 = img + (int64_t)y0 * w;
-    const float* r1 = img + (int64_t)y1 * w;
-    float v = r0[x0] * (wx0 * wy0);
-    v += r0[x1] * (wx1 * wy0);
-    v += r1[x0] * (wx0 * wy1);
-    v += r1[x1] * (wx1 * wy1);
-    return v;
-}
 
 // light_axis_to_cood, the table row of calc_inte_L_V, fh_n and calc_inte_L (sg_shadow.py:34-73, 143-144)
 __global__ void __launch_bounds__(256) ssdf_lights_kernel(const float* __restrict__ lSGs, int L,

@@ -10,7 +10,8 @@ and shadow steps consume the resulting (P,9,3) and (P,9,1) tensors.
 The helpers keep the reference's names, semantics and spelling
 (`clamp_postive`); they work on any device and run the HIP kernels
 (csrc/probe.hip) on CUDA fp32 contiguous inputs.  `sh_probes` renders and
-projects whole batches of probes on the device.
+projects whole batches of probes on the device; `sg_probe` renders one cube
+map and fits the SG lights of the SG shading path to it (sg_probe.py).
 """
 from __future__ import annotations
 
@@ -179,3 +180,23 @@ def sh_probes(model, pts, dirs=None, n_rays=2048, SH_bkg=None, blend_bkg=True, p
         res['opacity'] = torch.cat(rays['opacity'])[:P]
         res['dirs'] = dirs
     return res
+
+
+@torch.no_grad()
+def sg_probe(model, pt, env_opt, SH_bkg=None, resolution=32, env_hw=(128, 128), **render_kwargs):
+    """The SG light probe at the point pt (3,) (main.py:306-352 with SH_probe=False): a cube map of
+    6 * resolution^2 rays rendered from pt through sh_probes (one probe, probes_per_batch=1, SH_bkg blended in
+    behind the rays), resampled to an env_hw equirectangular map (sg_probe.cubemap2env_map), to which env_opt
+    (an sg_probe.EnvOptim: warm-started, N_iter Adam steps) fits its lights; trans_raw_sg normalises a copy of
+    them into the rows shading.sg_shade and sg_shadow.SGShadow take.
+
+    Returns {'lSGs': (L,7) axis, sharpness, rgb; 'envmap': (H,W,3); 'cubemap_rgb': (6*resolution^2,3)}."""
+    import sg_probe as SGP
+    res, (H, W) = int(resolution), (int(v) for v in env_hw)
+    dirs = get_cubemap_rays(1, res)[0]
+    out = sh_probes(model, torch.as_tensor(pt, dtype=torch.float32).reshape(1, 3), dirs=dirs, SH_bkg=SH_bkg,
+                    probes_per_batch=1, return_rays=True, **render_kwargs)
+    cubemap_rgb = out['rgb'][0].contiguous()
+    envmap = SGP.cubemap2env_map(cubemap_rgb, res, H, W)
+    lSGs = SGP.trans_raw_sg(env_opt.eval(envmap).clone())
+    return {'lSGs': lSGs, 'envmap': envmap, 'cubemap_rgb': cubemap_rgb}

@@ -421,6 +421,56 @@ int ngp_sg_shadow_frame_decay(const int32_t* bbox, int64_t H, int64_t W, const f
  * writer per pixel. */
 int ngp_shadow_apply(const float* frame_rgb, const float* factor, int64_t H, int64_t W, float* out_rgb, void* stream);
 
+/* ---- SG light probes: cube map -> env map -> SG fit ------
+ * What the insertion app's generate_probe(pt, SH_probe=False) (insert/main.py:
+ * 306-352) does after it has rendered the cube map: cubemap2env_map
+ * (insert/render_utils.py:117-189) and EnvOptim.eval (insert/envfit.py:
+ * 275-297), the Adam fit of n_lights spherical Gaussians to the env map.
+ * fp32 per (pixel, light) pair, no atomics, every result a function of the
+ * inputs alone.  Direction sets are (n,3) tensors: the kernels never form
+ * angles.  Raw light rows (n_lights,7) = lobe, sharpness, rgb amplitude as the
+ * optimiser holds them: a = lobe / (|lobe| + 1e-8), lam = |sharpness|,
+ * mu = |amplitude| (parse_raw_sg).  1 <= n_lights <= NGP_SG_FIT_MAX_LIGHTS.
+ * A pair's v . a - 1 is formed as (|v|^2-1)/2 + (|a|^2-1)/2 - |v-a|^2/2 with a
+ * held as a float pair (normalised in fp64 per light): fp32 per pair, but with
+ * roundings of the size of the result, not of the products (a sharp light's
+ * exponent multiplies them by its sharpness). */
+#define NGP_SG_FIT_MAX_LIGHTS 128
+/* pixels per block of the gradient launch (one row of the workspace each) */
+#define NGP_SG_FIT_BLOCK_PIXELS 64
+/* cubemap_sample(cubemap, dirs, res, None, False): cubemap (6*res*res,3),
+ * faces +z, -z, +x, -x, +y, -y, each (res,res,3).  Per direction: the axis of
+ * the largest |component| (ties: the lowest axis), divided by it; face
+ * {2,4,0}[axis] (+1 when the component is negative); the other two components
+ * (u, v), ascending axis order, address the face's first and second index;
+ * bilinear, pixel centres, border padding.  A direction whose largest
+ * |component| is 0 (or not finite) yields (1,1,1).  One lane per direction. */
+int ngp_cubemap_sample(const float* cubemap, int res, const float* dirs, int64_t n_dirs, float* rgb, void* stream);
+/* SG2Envmap: rgb[p] = sum_l mu_l exp(lam_l (dirs[p] . a_l - 1)), lights
+ * ascending; lgtSGs raw rows. */
+int ngp_sg_envmap(const float* lgtSGs, int n_lights, const float* dirs, int64_t n_pixels, float* rgb, void* stream);
+/* Bytes of ngp_sg_fit's workspace: doubles [blocks][n_lights][8], blocks =
+ * ceil(n_pixels / NGP_SG_FIT_BLOCK_PIXELS).  0: an argument is out of range. */
+int64_t ngp_sg_fit_workspace_bytes(int64_t n_pixels, int n_lights);
+/* n_iter Adam iterations on mse(SG2Envmap(lgtSGs), target), two launches
+ * each.  Gradient launch: a block owns NGP_SG_FIT_BLOCK_PIXELS pixels, forms
+ * each pixel's env value (lights ascending, as ngp_sg_envmap) and residual r,
+ * g = 2 r / (3 n_pixels), s = mu . g, and writes its partial sums (fp64, fixed
+ * order) of e g_c, s e (dot - 1), s e lam v per light and of r^2 (slot [0][7])
+ * to its row of the workspace.  Step launch (one block): one owner per sum
+ * adds the rows in ascending block order; the chain rule of abs (sign(0) = 0)
+ * and of the normalisation (dx = da/(n+eps) - x (da.x) / (n (n+eps)^2), the
+ * second term 0 for a zero lobe, as torch's norm backward is) gives grad
+ * (n_lights,7); losses[i] = the mse before iteration
+ * i's step; then torch.optim.Adam's step (betas 0.9, 0.999, eps 1e-8, denom =
+ * sqrt(v)/sqrt(1 - b2^t) + eps, step = lr / (1 - b1^t)) on lgtSGs, exp_avg,
+ * exp_avg_sq with t = ++*step (device int64).  grad holds the last
+ * iteration's gradient.  n_iter == 0 is a no-op.  Nothing allocates or
+ * synchronises: a captured chain replays. */
+int ngp_sg_fit(float* lgtSGs, int n_lights, const float* dirs, const float* target, int64_t n_pixels, int n_iter,
+               float lr, float* exp_avg, float* exp_avg_sq, int64_t* step, void* workspace, float* grad,
+               float* losses, void* stream);
+
 /* ------------------------------------------------------- light probes */
 /* The insertion app's light probes (insert/main.py:306-407): R rays from each
  * of P scene points, the global light blended in behind them as an SH9
